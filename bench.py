@@ -1,6 +1,7 @@
 """bench.py -- MI355X monotonic RNN-T loss+grad throughput (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c2|ragged|ragged64|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config headline|c2|ragged|ragged64|c5] [--full]
+                  [--dump-outputs DIR]
 
 One step = forward (log-softmax row reduce + alpha/beta DP) + backward (logit gradient, dL/dcost fused)
 over one batch through the autograd surface (monotonic_rnnt_loss(...).sum().backward()), plus, for N > 1,
@@ -18,8 +19,13 @@ not fit (configs[3] at N = 1: 292 GB) runs as chunks of utterances. In those two
 regenerated before each chunk outside the timed intervals, and the step time is the sum of the timed chunk
 intervals (each bracketed by barrier + synchronize).
 
-Rank 0 prints ONE JSON line with the contract fields plus:
-  roofline     : the gradient kernel (dominant): algorithmic bytes (N_live + N) * V * elem of its launches (N_live =
+A plain run does what the headline figure needs and no more: set up, warm up, time the K steps, write the last
+step's outputs when --dump-outputs DIR is given (costs.npy, and grads_sample.npy / grads_sample_rows.npy: a fixed
+seeded sample of the gradient rows; the inputs of two runs with the same arguments are identical), and print ONE
+JSON line on rank 0: the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step), the
+configuration, every rank's step time and loss_check (the summed loss of the last step). Every other measurement
+runs after that only under --full, and adds to the line:
+  roofline    : the gradient kernel (dominant): algorithmic bytes (N_live + N) * V * elem of its launches (N_live =
                  in-band rows whose fp32 gradient is not exactly zero, the rows it reads) divided by their duration
                  from HIP events recorded around each launch on its stream in the timed region; the SURVEY §8d
                  formula (N_v + N) * V * 4 is reported beside it as formula_bytes_per_launch / formula_gbps
@@ -28,6 +34,8 @@ Rank 0 prints ONE JSON line with the contract fields plus:
                  concurrent calls of at most the reference's 32-bit-offset utterance count each; the library's
                  own host implementation (RNNT_CPU) on the same sample is reported beside it
   kernels      : per-kernel average ms and achieved GB/s
+  lengths_ab   : the other lengths form (host / device tensors) timed in the same process
+  ranks.allreduce_4byte_us : the loss all-reduce timed alone (N > 1)
 """
 import argparse
 import ctypes
@@ -46,6 +54,16 @@ sys.path.insert(0, os.path.join(ROOT, "monotonic-rnnt_amd", "pytorch_binding"))
 
 METRIC = "utterances/sec + achieved HBM GB/s, (B,T,S,V)=(64,1000,200,1024)"
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md chip table)
+DUMP_GRAD_BYTES = 48 << 20  # --dump-outputs: bytes of gradient rows written, all ranks together (under 64 MB in all)
+
+
+def dump_rows(n_rows, V, budget_bytes):
+    """The gradient rows --dump-outputs writes: every row when they fit the budget as float32, else a sorted sample
+    without replacement drawn with a fixed seed (the same rows in every run of the same arguments)."""
+    n = max(1, budget_bytes // (V * 4))
+    if n >= n_rows:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(2024).choice(n_rows, n, replace=False)).astype(np.int64)
 
 
 def ragged_lengths():
@@ -107,7 +125,17 @@ def parse():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="headline", choices=["headline", "c2", "ragged", "ragged64", "c5", "halo"])
-    ap.add_argument("--cpu-sample", type=int, default=16, help="utterances in the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: roofline (live "
+                         "rows, PMC traffic record, copy / read probes), per-kernel rates, the other lengths form "
+                         "(lengths_ab), the CPU baseline, the all-reduce latency, per-kernel times under --graph")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32; row indices float64): costs, and a fixed seeded sample of the "
+                         "gradient rows (grads_sample, grads_sample_rows); with --gpus N > 1 every rank writes its own "
+                         "files, suffixed _rank<r>")
+    ap.add_argument("--cpu-sample", type=int, default=16,
+                    help="utterances in the CPU-baseline sample of --full (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads for the CPU baseline (0 = this process's CPU share: affinity / cgroup quota)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -169,6 +197,8 @@ def main():
     args = parse()
     if args.cpu_worker:
         return cpu_worker(json.loads(args.cpu_worker))
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -303,6 +333,12 @@ def run(args, world):
     lengths_ab = None
     if args.graph and mode != "resident":
         raise SystemExit("--graph needs a resident config")
+    dump = None
+    if args.dump_outputs:
+        # the gradient rows written out: a fixed, seeded choice within a byte budget shared by the ranks
+        pick = dump_rows(rows, V, DUMP_GRAD_BYTES // world)
+        dump = {"grads_sample_rows": pick.astype(np.float64)}
+    last = {}  # the costs tensor of the latest step (what monotonic_rnnt_loss returned to its caller)
     if mode == "resident":
         acts = synth(0, B)
         if args.acts_dtype != "f32":
@@ -314,6 +350,7 @@ def run(args, world):
 
         def loss_and_grad(Tl, Sl):
             costs = op.monotonic_rnnt_loss(acts, labels_dev, Tl, Sl, align, args.align_k or 0, blank_label=0)
+            last["costs"] = costs.detach()  # (no grad_fn: holds the B costs, not the step's workspace)
             loss = costs.sum()
             loss.backward()
             return loss
@@ -370,14 +407,17 @@ def run(args, world):
         L.profile_enable(not args.graph)
         elapsed, loss = timed_steps(step, args.steps)
         loss_val = loss.detach().reshape(1).double()
-        if args.graph:  # replays launch no kernels from the host: per-kernel times from eager steps after timing
+        if dump is not None:  # before anything below runs further steps or probes over these buffers
+            dump["costs"] = last["costs"].float().cpu().numpy()
+            dump["grads_sample"] = acts.grad.index_select(0, torch.from_numpy(pick).to(dev)).float().cpu().numpy()
+        if args.graph and args.full:  # replays launch no kernels from the host: per-kernel times from eager steps after timing
             L.profile_enable(True)
             for _ in range(prof_steps):
                 eager_step()
             torch.cuda.synchronize()
         prof_main = L.profile_read()
         L.profile_enable(False)
-        if not args.no_lengths_ab:
+        if args.full and not args.no_lengths_ab:
             # the other lengths form, same process, buffers and step count, after the measured steps (not in `value`)
             other = (T_h, S_h) if device_lengths else (T_g, S_g)
             step_o, _ = make_steps(*other)
@@ -413,9 +453,17 @@ def run(args, world):
                 chunk_step(lo, hi)
         L.profile_enable(True)
         elapsed = 0.0
-        for _ in range(args.steps):
+        picked = []
+        for s in range(args.steps):
             for lo, hi in chunks:
                 elapsed += chunk_step(lo, hi)
+                if dump is not None and s == args.steps - 1:
+                    # the chunk's gradients stand in the logits' buffer until the next chunk is generated over them
+                    loc = pick[(pick >= crow[lo]) & (pick < crow[hi])] - int(crow[lo])
+                    picked.append(acts_buf.index_select(0, torch.from_numpy(loc).to(dev)).cpu().numpy())
+        if dump is not None:
+            dump["costs"] = costs_c.cpu().numpy()
+            dump["grads_sample"] = np.concatenate(picked)
         loss_val = costs_c.double().sum().reshape(1)
         acts = None
         prof_main = L.profile_read()
@@ -433,11 +481,60 @@ def run(args, world):
         dist.all_gather(g, el)
         rank_elapsed = [float(x.item()) for x in g]
     elapsed = max(rank_elapsed)
-    ar_us = allreduce_latency_us(dist, coll, torch, dev, world)
+    if dump is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+    ar_us = allreduce_latency_us(dist, coll, torch, dev, world) if args.full else None
     total_utts = coll(torch.tensor([B], dtype=torch.int64, device=dev))
     if world > 1:
         dist.all_reduce(total_utts)
     total_utts = int(total_utts.item())
+
+    n_chunks = len(chunks)
+    base = {
+        "metric": METRIC,
+        "value": round(total_utts * args.steps / elapsed, 3),
+        "unit": "utt/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": args.acts_dtype,
+        "data": f"synthetic: counter-hash {'N(0,1)-like' if normal else 'U[0,1)'} acts (seed 0), labels U[1,V-1] (seed 1+rank; configs[3]: seed 1 over the global batch); inputs resident in HBM",
+        "config": {"workload": workload, "utterances_per_gpu": B, "global_batch": total_utts,
+                   "rows_per_gpu": rows, "inband_rows_per_gpu": n_band, "V": V,
+                   "acts_dist": args.acts_dist, "memory_mode": mode, "chunks_per_step": n_chunks,
+                   "execution": "hip_graph_replay" if args.graph else "eager",
+                   "lengths": "device" if (device_lengths or mode != "resident") else "host",
+                   "rank_devices": rank_devices,
+                   **({"window_rows_per_gpu": n_window} if n_window is not None else {}),
+                   "parallelism": f"dp{world} (batch-sharded, one 4-byte "
+                                  f"{'gloo (rehearsal)' if gloo else 'RCCL'} loss all-reduce)"},
+        # what the driver needs to compare N > 1 with N = 1: every rank's own step time (value uses the max),
+        # their spread, and (--full) the loss all-reduce's own latency, timed alone after the steps, max over ranks
+        "ranks": {"n": world, "ms_per_step": [round(e * 1e3 / args.steps, 4) for e in rank_elapsed],
+                  "max_ms_per_step": round(max(rank_elapsed) * 1e3 / args.steps, 4),
+                  "min_ms_per_step": round(min(rank_elapsed) * 1e3 / args.steps, 4),
+                  "balance_min_over_max": round(min(rank_elapsed) / max(rank_elapsed), 4),
+                  "devices_distinct": len({(d["device"], d["pci_bus"], d["pci_device"])
+                                           for d in rank_devices}) == world,
+                  "allreduce_4byte_us": ar_us,
+                  "collective": "none" if world == 1 else ("gloo (rehearsal)" if gloo else "RCCL")},
+        "grads_placement": placement_log(),
+        "tune": args.tune or None,
+        "loss_check": loss_val,
+        "full": args.full,
+    }
+    if not args.full:  # a plain run ends here: the headline figure and what the timed steps themselves left behind
+        if rank == 0:
+            print(json.dumps(base), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # live rows: in-band rows whose gradient is not exactly zero in fp32 -- the only acts rows the gradient
     # kernel reads (occupancy skip); counted once after the timed region
@@ -450,7 +547,6 @@ def run(args, world):
     n_read = n_band if n_window is None else n_window  # rows the log-softmax pass reads
     softmax_bytes = n_read * V * elem
     step_bytes = (n_read + live + rows) * V * elem
-    n_chunks = len(chunks)
 
     def tot_ms(name):
         ms, n = prof[name]
@@ -497,27 +593,7 @@ def run(args, world):
 
     if rank == 0:
         out = {
-            "metric": METRIC,
-            "value": round(total_utts * args.steps / elapsed, 3),
-            "unit": "utt/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": args.acts_dtype,
-            "data": f"synthetic: counter-hash {'N(0,1)-like' if normal else 'U[0,1)'} acts (seed 0), labels U[1,V-1] (seed 1+rank; configs[3]: seed 1 over the global batch); inputs resident in HBM",
-            "config": {"workload": workload, "utterances_per_gpu": B, "global_batch": total_utts,
-                       "rows_per_gpu": rows, "inband_rows_per_gpu": n_band, "V": V,
-                       "acts_dist": args.acts_dist, "memory_mode": mode, "chunks_per_step": n_chunks,
-                       "execution": "hip_graph_replay" if args.graph else "eager",
-                       "lengths": "device" if (device_lengths or mode != "resident") else "host",
-                       "rank_devices": rank_devices,
-                       **({"window_rows_per_gpu": n_window} if n_window is not None else {}),
-                       "parallelism": f"dp{world} (batch-sharded, one 4-byte "
-                                      f"{'gloo (rehearsal)' if gloo else 'RCCL'} loss all-reduce)"},
+            **base,
             "achieved_hbm_gbps_step": round(step_bytes * args.steps / elapsed / 1e9, 1),
             "roofline": {"kernel": "logit gradient", "bound": "hbm",
                          "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBPS,
@@ -543,20 +619,7 @@ def run(args, world):
                 "grad": {"avg_ms": round(g_avg, 4) if g_avg else None, "gbps": round(achieved, 1) if achieved else None},
             },
             "cpu_baseline": cpu,
-            # what the driver needs to compare N > 1 with N = 1: every rank's own step time (value uses the max),
-            # their spread, and the loss all-reduce's own latency (timed alone after the steps, max over ranks)
-            "ranks": {"n": world, "ms_per_step": [round(e * 1e3 / args.steps, 4) for e in rank_elapsed],
-                      "max_ms_per_step": round(max(rank_elapsed) * 1e3 / args.steps, 4),
-                      "min_ms_per_step": round(min(rank_elapsed) * 1e3 / args.steps, 4),
-                      "balance_min_over_max": round(min(rank_elapsed) / max(rank_elapsed), 4),
-                      "devices_distinct": len({(d["device"], d["pci_bus"], d["pci_device"])
-                                               for d in rank_devices}) == world,
-                      "allreduce_4byte_us": ar_us,
-                      "collective": "none" if world == 1 else ("gloo (rehearsal)" if gloo else "RCCL")},
             "lengths_ab": lengths_ab,
-            "grads_placement": placement_log(),
-            "tune": args.tune or None,
-            "loss_check": loss_val,
         }
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -28,3 +28,17 @@ def test_bad_options_fail_before_the_gpu(args, msg):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True,
                        timeout=120)
     assert r.returncode != 0 and msg in r.stderr, r.stderr[-2000:]
+
+
+def test_dump_rows_are_fixed_and_within_budget():
+    """The gradient rows --dump-outputs writes: every row of a small output, else the same sorted sample of distinct
+    rows in every run, within the byte budget as float32."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert np.array_equal(bench.dump_rows(5, 8, 1 << 20), np.arange(5))
+    a = bench.dump_rows(12_864_000, 1024, bench.DUMP_GRAD_BYTES)
+    b = bench.dump_rows(12_864_000, 1024, bench.DUMP_GRAD_BYTES)
+    assert np.array_equal(a, b) and a.dtype == np.int64
+    assert len(a) * 1024 * 4 <= bench.DUMP_GRAD_BYTES < 64e6 and len(a) == bench.DUMP_GRAD_BYTES // 4096
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 12_864_000

@@ -215,12 +215,37 @@ def test_bench_launches_two_ranks():
 def test_bench_chunked_in_place_mode_matches_resident():
     """The in-place / chunked memory modes (configs[3] at N <= 2, configs[4]) compute the same loss as the
     resident autograd path on a small config forced into chunks by a tiny HBM budget."""
-    res = _bench(["--config", "c2", "--steps", "1", "--warmup", "1", "--no-cpu"])
-    chk = _bench(["--config", "c2", "--steps", "1", "--warmup", "1", "--no-cpu", "--hbm-budget-gb", "0.05"])
+    res = _bench(["--config", "c2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu"])
+    chk = _bench(["--config", "c2", "--steps", "1", "--warmup", "1", "--full", "--no-cpu", "--hbm-budget-gb", "0.05"])
     assert res["config"]["memory_mode"] == "resident" and chk["config"]["memory_mode"] == "inplace"
     assert chk["config"]["chunks_per_step"] > 1
     assert abs(res["loss_check"] - chk["loss_check"]) <= 1e-5 * abs(res["loss_check"])
     assert res["roofline"]["live_rows"] == chk["roofline"]["live_rows"]
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run prints the headline figure without the --full measurements, and --dump-outputs writes what the
+    last timed step returned: every cost (their sum is the line's loss_check) and the sampled gradient rows (the
+    fixed choice of dump_rows), float32, each row summing to zero over the vocabulary."""
+    out = _bench(["--config", "c2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] is False
+    assert abs(out["value"] - 16 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert not {"roofline", "kernels", "cpu_baseline", "lengths_ab"} & set(out)
+    assert sorted(os.listdir(tmp_path)) == ["costs.npy", "grads_sample.npy", "grads_sample_rows.npy"]
+    costs = np.load(tmp_path / "costs.npy")
+    grads = np.load(tmp_path / "grads_sample.npy")
+    picked = np.load(tmp_path / "grads_sample_rows.npy")
+    assert costs.dtype == np.float32 and costs.shape == (16,) and np.all(np.isfinite(costs))
+    assert abs(float(costs.astype(np.float64).sum()) - out["loss_check"]) <= 1e-5 * abs(out["loss_check"])
+    import bench
+    n = out["config"]["rows_per_gpu"]
+    want = bench.dump_rows(n, 256, bench.DUMP_GRAD_BYTES)
+    assert n == 16 * 200 * 41 and len(want) == bench.DUMP_GRAD_BYTES // 1024 < n
+    assert picked.dtype == np.float64 and np.array_equal(picked, want)
+    assert grads.dtype == np.float32 and grads.shape == (len(want), 256) and np.all(np.isfinite(grads))
+    # a row's entries are exp() of fp32 log-domain sums up to ~110 in magnitude (rounded to 110 * 2^-24 = 7e-6
+    # relative) and their absolute sum is at most 2: the bound the sharded configs[3] test uses covers it
+    assert np.any(grads != 0) and np.max(np.abs(grads.astype(np.float64).sum(axis=1))) < 1e-4
 
 
 def test_fill_zero(dev):
@@ -376,7 +401,7 @@ def test_hip_graph_capture_replay(op, dev, aligned, device_lengths):
 def test_bench_graph_mode_matches_eager():
     """`bench.py --graph` (forward + backward replayed from a HIP graph) computes the loss of the eager step."""
     eager = _bench(["--config", "c2", "--steps", "5", "--warmup", "2", "--no-cpu"])
-    graph = _bench(["--config", "c2", "--steps", "20", "--warmup", "3", "--no-cpu", "--graph"])
+    graph = _bench(["--config", "c2", "--steps", "20", "--warmup", "3", "--full", "--no-cpu", "--graph"])
     assert graph["config"]["execution"] == "hip_graph_replay" and eager["config"]["execution"] == "eager"
     assert abs(graph["loss_check"] - eager["loss_check"]) <= 1e-6 * abs(eager["loss_check"])
     assert graph["kernels"]["grad"]["avg_ms"] > 0 and graph["ms_per_step"] > 0
@@ -387,7 +412,7 @@ def test_bench_eight_rank_rehearsal():
     weak-scaled (8 x 16 utterances) and configs[3] strong-scaled in in-place chunks under a small HBM budget, whose
     all-reduced loss equals the one-rank run over the same 512 utterances. Every rank reports its device."""
     c2 = _bench(["--gpus", "8", "--dist-backend", "gloo", "--config", "c2", "--steps", "2", "--warmup", "1",
-                 "--no-cpu"], 400)
+                 "--full", "--no-cpu"], 400)
     assert c2["n_gpus"] == 8 and c2["config"]["global_batch"] == 128 and c2["scaling"] == "weak"
     assert sorted(d["rank"] for d in c2["config"]["rank_devices"]) == list(range(8))
     assert {d["local_rank"] for d in c2["config"]["rank_devices"]} == set(range(8))

@@ -8,7 +8,7 @@ O=$R/gpurun_out/prof_${TAG}_${CONFIG}_${DTYPE}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --config $CONFIG --acts-dtype $DTYPE"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $B --steps $STEPS --no-cpu > $O/bench_prof.json 2> $O/bench_prof.err && \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 $B --steps $STEPS --full --no-cpu > $O/bench_prof.json 2> $O/bench_prof.err && \
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 $B --steps 3 --warmup 1 --no-cpu > $O/pmc_fetch.json 2> $O/pmc_fetch.err && \
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d $O/write -o run --output-format csv -- python3 $B --steps 3 --warmup 1 --no-cpu > $O/pmc_write.json 2> $O/pmc_write.err && \
 python3 $R/tools/pmc_summary.py --stats $O/stats --fetch $O/fetch --write $O/write --bench $O/bench_prof.json --tag $TAG --config $CONFIG --dtype $DTYPE > $O/summary.json && \

@@ -31,7 +31,7 @@ def main():
         ranks = []
         for r in range(n):
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "ragged", "--shard", f"{r}/{n}",
-                   "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu"]
+                   "--steps", str(a.steps), "--warmup", str(a.warmup), "--full", "--no-cpu"]
             out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
             if out.returncode != 0:
                 raise SystemExit(f"shard {r}/{n} failed:\n{out.stderr[-3000:]}")
