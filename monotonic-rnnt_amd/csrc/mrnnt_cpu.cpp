@@ -111,10 +111,12 @@ __attribute__((target("avx512f,avx512dq,avx512bw,avx512vl,fma"))) void grad_row(
 }
 
 // log(e^x + e^y) with fp64 state (rnnt_helper.h:16-30): one -inf input returns the other exactly, both
-// -inf is -inf, NaN propagates (the HIP path's lse2 in mrnnt_device.h has the same cases).
+// -inf is -inf, NaN propagates (the HIP path's lse2 in mrnnt_device.h has the same cases). fmax drops a NaN
+// operand, so the -inf case tests both operands: (NaN, -inf) -- every band-edge cell below a NaN row -- is NaN
+// through x - y, not "no path".
 inline double lse(double x, double y) {
     const double m = std::fmax(x, y);
-    if (m == kNegInf) return kNegInf;
+    if (x == kNegInf && y == kNegInf) return kNegInf;
     return m + std::log1p(std::exp(-std::fabs(x - y)));
 }
 

@@ -27,7 +27,9 @@ __device__ __forceinline__ float fast_log2(float x) { return __builtin_amdgcn_lo
 // correction (in [0, ln 2]) is log2(1 + e) * ln 2 on the fp32 hardware exp2/log2: <= ~1e-7 absolute per step (the
 // rounding of 1 + e to fp32, 6e-8, plus v_log_f32's). The classic log1p rounding fix (((u - 1) - e) / u) halved that
 // but put three more dependent operations on the one-wave recursion's chain. One -inf input gives
-// d = -inf, e = 0, r = m exactly; both -inf is the only NaN case and is patched to -inf.
+// d = -inf, e = 0, r = m exactly; both -inf makes d NaN and is patched to -inf. A NaN input propagates: v_max_f64
+// drops it from m, but d (and so r) is NaN -- which is why the patch tests both operands, not m (m == -inf also holds
+// for (NaN, -inf), the case of every band-edge cell below a NaN row, and would report "no path" for bad input).
 __device__ __forceinline__ double max_f64(double x, double y) {
     // v_max_f64 without the canonicalising max fmax() emits for an operand the compiler cannot prove canonical (a DPP
     // result): the same value for every non-NaN input, one instruction fewer per recursion step
@@ -42,12 +44,13 @@ __device__ __forceinline__ double lse2(double x, double y) {
     const float e = fast_exp2(d * kLog2e);
     const float c = fast_log2(1.0f + e) * kLn2;
     const double r = m + (double)c;
-    return (m == NEG_INF_D) ? NEG_INF_D : r;
+    return (x == NEG_INF_D && y == NEG_INF_D) ? NEG_INF_D : r;
 }
 
 // log(e^x + e^y + e^z), the same form with three terms: m + log(sum e^(x_i - m)), the sum in [1, 3] in fp32 (one
 // term is exactly 1), log2 on v_log_f32 -- <= ~2e-7 absolute, the error of two lse2 steps, for a step that replaces
-// two of them on a dependent chain (the staged walk's frame pairs, mrnnt_chase.hip). All -inf gives -inf.
+// two of them on a dependent chain (the staged walk's frame pairs, mrnnt_chase.hip). All -inf gives -inf; a NaN
+// input gives NaN (through its own exp term), whatever the other two are.
 __device__ __forceinline__ double lse3(double x, double y, double z) {
     const double m = max_f64(max_f64(x, y), z);
     const float ex = fast_exp2((float)(x - m) * kLog2e);
@@ -55,7 +58,7 @@ __device__ __forceinline__ double lse3(double x, double y, double z) {
     const float ez = fast_exp2((float)(z - m) * kLog2e);
     const float c = fast_log2(ex + ey + ez) * kLn2;
     const double r = m + (double)c;
-    return (m == NEG_INF_D) ? NEG_INF_D : r;
+    return (x == NEG_INF_D && y == NEG_INF_D && z == NEG_INF_D) ? NEG_INF_D : r;
 }
 
 // wave64 butterfly reduction of an online-softmax (max, sum-exp) pair
@@ -339,13 +342,13 @@ __device__ __forceinline__ void align_window(const DevProblem &p, int64_t c, int
 
 // Label of row s as the log-softmax kernels use it (has = s < S). Device labels are not range-checked on the
 // host (that would need a sync), so a label outside [0, V) reads no logit: it is returned as -1 (no capture)
-// and the row's label logit `ze` starts as NaN: the transitions through that label carry NaN, which the
-// recursion turns into NaN or no probability, so the utterance's cost is not finite (NaN / +inf) and its
-// gradient non-finite.
+// and the row's label logit `ze` starts as -inf: the transitions through that label carry no probability, every
+// path of the utterance crosses one of them, so its cost is +inf ("no path") and its gradient NaN (exp(... - ll),
+// ll = -inf). (Not NaN: the recursion's LSE propagates a NaN, and a NaN cost means a NaN logit.)
 // A row without a label (s == S) returns -1 with ze = 0.
 __device__ __forceinline__ int checked_label(bool has, int l, int V, float &ze) {
     const bool bad = has && (unsigned)l >= (unsigned)V;
-    ze = bad ? __builtin_nanf("") : 0.0f;
+    ze = bad ? NEG_INF_F : 0.0f;
     return (has && !bad) ? l : -1;
 }
 

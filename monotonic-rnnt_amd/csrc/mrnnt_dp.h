@@ -109,7 +109,7 @@ __device__ __forceinline__ void alpha_pass_halo(const DevProblem &p, const Utt &
     for (int d = 0; d < D; ++d) {
         const int tt = min(d, T - 1);
         if constexpr (CH) ch->gate(tt);
-        const Lp l = LEAN ? ld(p.lp + (r0 + (int64_t)tt * W)) : p.lp[r0 + (int64_t)tt * W + s0];
+        const Lp l = LEAN ? ld(p.lp + (r0 + (int64_t)tt * W)) : p.lp[r0 + (int64_t)tt * W + sl];
         pb[d] = l.b;
         pe[d] = l.e;
         mn[d] = BAND ? p.min_s[c0 + tt] : 0;
@@ -159,7 +159,9 @@ __device__ __forceinline__ void alpha_pass_halo(const DevProblem &p, const Utt &
         a = (s0 >= lo && s0 <= hi) ? v : NEG_INF_D;
         if (own) p.alpha[r0 + (int64_t)t * W + s0] = a;
         const int tn = min(t + D, T - 1);
-        const Lp l = p.lp[r0 + (int64_t)tn * W + s0];
+        // (sl: the halo lanes of wave 0 read cell 0 like the lean step -- the rows before this frame's, at t = 0 the
+        // previous utterance's, may hold a NaN, and lane s = -1 hands -inf + its lpe to cell 0)
+        const Lp l = p.lp[r0 + (int64_t)tn * W + sl];
         pb[d] = l.b;
         pe[d] = l.e;
         mn[d] = BAND ? p.min_s[c0 + tn] : 0;
@@ -215,8 +217,10 @@ __device__ __forceinline__ void beta_pass_halo(const DevProblem &p, const Utt &u
     const bool own = lane < C && s0 < W;
     const unsigned sl = (unsigned)s0;
     // CH: lp rows read only inside this utterance's column: the cells above S (which stay -inf) read row S instead
-    // (clamped offset, unconditional load; as alpha_pass_halo)
-    const unsigned slc = CH ? min(sl, (unsigned)S) : sl;
+    // (clamped offset, unconditional load; as alpha_pass_halo). Without the chase the clamp matters to the one-wave
+    // pass (HL = 0), whose lanes past S are not masked: a lane past S would read the rows that follow in lp -- the
+    // next utterance's -- and a NaN there (a NaN logit of that utterance) would come down the carry into cell S.
+    const unsigned slc = min(sl, (unsigned)S);
     auto ld = [&](const Lp *row) -> Lp {
         if constexpr (CH)
             return load_lp_wt(lp_rsrc(p), slc * (unsigned)sizeof(Lp), (unsigned)((row - p.lp) * (int64_t)sizeof(Lp)));
@@ -289,7 +293,7 @@ __device__ __forceinline__ void beta_pass_halo(const DevProblem &p, const Utt &u
         bn = (s0 >= lo && s0 <= hi) ? v : NEG_INF_D;
         if (own) p.beta[r0 + (int64_t)t * W + s0] = bn;
         const int tn = max(t - D, 0);
-        const Lp l = p.lp[r0 + (int64_t)tn * W + s0];
+        const Lp l = p.lp[r0 + (int64_t)tn * W + slc];  // (clamped like ld(): the lanes past S are masked anyway)
         pb[d] = l.b;
         pe[d] = l.e;
         mn[d] = (BAND && tn > 0) ? p.min_s[c0 + tn - 1] : 0;

@@ -37,8 +37,8 @@ __device__ __forceinline__ void zero_fill_outside_band(const DevProblem &p, int6
 }
 
 // The 64 lp entries either side of [0, N): the recursion's in-band cell s = 0 of utterance 0 adds lpe[-1] to its
-// -inf predecessor, and a NaN / +inf left in the (reused) workspace there would turn alpha(0, 0) into NaN (then
-// -inf through fmax in the next LSE: an infinite cost). Zeroed by the first workgroup of every log-softmax launch.
+// -inf predecessor, and a NaN / +inf left in the (reused) workspace there would turn alpha(0, 0) into NaN (and the
+// cost with it: the LSE propagates NaN). Zeroed by the first workgroup of every log-softmax launch.
 __device__ __forceinline__ void zero_lp_pads(const DevProblem &p) {
     if (blockIdx.x == 0 && threadIdx.x < 64) {
         const int i = threadIdx.x;

@@ -43,7 +43,7 @@ __device__ __forceinline__ void alpha_pass(const DevProblem &p, int b, float *__
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             pb[d][k] = rl[k].b;
-            pe[d][k] = rl[k - 1].e;
+            pe[d][k] = (s0 + k == 0) ? 0.0 : rl[k - 1].e;  // cell 0 has no s - 1 (see the step's reload)
         }
         mn[d] = band ? p.min_s[c0 + tt] : 0;
         mx[d] = band ? p.max_s[c0 + tt] : S;
@@ -79,7 +79,10 @@ __device__ __forceinline__ void alpha_pass(const DevProblem &p, int b, float *__
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 pb[d][k] = rl[k].b;
-                pe[d][k] = rl[k - 1].e;
+                // cell 0 adds its lpe to the -inf of alpha(t-1, -1): rl[-1] is the row before this frame's -- at
+                // t = 0 the previous utterance's last row -- and a NaN there (a NaN logit of that utterance) would
+                // make alpha(t, 0) NaN; the term is -inf whatever the row holds
+                pe[d][k] = (s0 + k == 0) ? 0.0 : rl[k - 1].e;
             }
             mn[d] = band ? p.min_s[c0 + tn] : 0;
             mx[d] = band ? p.max_s[c0 + tn] : S;

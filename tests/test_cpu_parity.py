@@ -15,6 +15,7 @@ import torch
 
 import oracle as O
 from _parity import FIXTURES, assert_costs, assert_grads, assert_state, random_problem, used_rows
+from _value_domain import assert_costs_classed
 
 import monotonic_rnnt_op as op
 import _mrnnt_lib as L
@@ -184,6 +185,7 @@ def test_infeasible_alignment_inf_nan(V):
     assert np.isinf(cr[0]) and np.isinf(c[0])
     assert not np.isfinite(g[: 15 * 6]).any()
     assert_costs(c, cr)
+    assert_costs_classed(c, cr)  # the class too: +inf ("no path"), not NaN
     assert_grads(g, gr)
 
 

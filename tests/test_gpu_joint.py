@@ -412,6 +412,45 @@ def test_joint_weight_bound_edge(jop, dev, over):
     _check_vs_host(jop, dev, enc, pred, w, bias, labels, T, S)
 
 
+def test_joint_masked_bias(jop, dev):
+    """Vocabulary entries masked with bias = -inf (ordinary in training): half of the entries that are neither the
+    blank nor a label, entry V - 1 (the tail chunk's last column) among them. The masked logits are -inf in every
+    row, so against the host reference at this file's tolerances and, exactly: d_bias and the rows of d_weight of the
+    masked entries are 0 (their softmax probability is e^-inf), and no gradient holds a NaN (-inf - -inf, 0 * inf).
+    The weight bound sum |W_v| + |b_v| is +inf, so the forward takes the running-max epilogue, not the plain exp-sum:
+    the development build gives the same bits with the running max forced on (joint_probe bit 3) as without."""
+    H, V = 256, 130
+    enc, pred, w, bias, labels, T, S = make_case(H + V + 9, 3, (10, 30), 8, H, V)
+    labels = np.where(labels == V - 1, 1, labels).astype(np.int32)
+    rng = np.random.default_rng(9)
+    free = np.array([v for v in range(1, V - 1) if v not in set(labels.reshape(-1).tolist())])
+    masked = np.concatenate([[V - 1], rng.choice(free, (len(free) + 1) // 2 - 1, replace=False)])
+    bias = bias.clone()
+    bias[torch.from_numpy(masked)] = -float("inf")
+    scale = [1.0, -0.5, 2.0]
+    c, de, dp, dw, db = run_joint(jop, dev, enc, pred, w, bias, labels, T, S, scale=scale)
+    cr, de_r, dp_r, dw_r, db_r = host_reference(enc, pred, w, bias, labels, T, S, scale=scale)
+    assert np.all(np.isfinite(cr)) and float(db_r.abs()[masked].max()) == 0.0  # the reference itself
+    assert np.all(np.isfinite(c)), c
+    assert np.all(np.abs(c - cr) <= 1e-5 * np.maximum(1.0, np.abs(cr))), (c, cr)
+    for x, name in ((de, "d_enc"), (dp, "d_pred"), (dw, "d_weight"), (db, "d_bias")):
+        assert not torch.isnan(x).any(), name
+    close(de, de_r, name="d_enc")
+    close(dp, dp_r, name="d_pred")
+    close(dw, dw_r, name="d_weight")
+    close(db, db_r, name="d_bias")
+    m = torch.from_numpy(masked).to(dev)
+    assert torch.all(db[m] == 0), db[m]
+    assert torch.all(dw[m] == 0), dw[m].abs().max()
+    with knobs(joint_probe=0):
+        own = run_joint(jop, dev, enc, pred, w, bias, labels, T, S, scale=scale)
+    with knobs(joint_probe=8):
+        forced = run_joint(jop, dev, enc, pred, w, bias, labels, T, S, scale=scale)
+    assert np.array_equal(own[0], forced[0])
+    for a, b in zip(own[1:], forced[1:]):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("H,V", [(512, 1024), (256, 1000), (640, 130)])
 def test_joint_plain_exp_sum_matches_running_max(dev, H, V):
     """Bounded weights: the plain exp-sum forward (product) against the running-max epilogue forced on (development

@@ -14,6 +14,7 @@ import torch
 
 import oracle as O
 from _parity import knobs as knobs_ctx
+from _value_domain import assert_costs_classed
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +167,7 @@ def test_infeasible_alignment_matches_reference_inf_nan(op, dev, V):
     assert np.isinf(cr[0]) and np.isinf(c[0])
     assert not np.isfinite(g[: 15 * 6]).any()
     assert_costs(c, cr)
+    assert_costs_classed(c, cr)  # the class too: +inf ("no path"), not NaN
     assert_grads(g, gr)
 
 

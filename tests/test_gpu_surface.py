@@ -60,8 +60,8 @@ def test_golden_denominators_alpha_beta(op, dev, path):
 @pytest.mark.parametrize("bad", [3, 7, -5, 1 << 30])
 def test_device_label_out_of_range_gives_inf_cost_nan_grads(op, dev, bad):
     """A device label outside [0, V) is not read back (no sync) and never used as an index: its log-softmax pick is
-    NaN, and the recursion's LSE turns a NaN transition into no probability (fmax drops the NaN; both directions
-    stay -inf past that label position, which every path of the utterance crosses). So, pinned exactly, whatever
+    -inf, a transition with no probability (both directions stay -inf past that label position, which every path
+    of the utterance crosses; a NaN pick would now come out as a NaN cost). So, pinned exactly, whatever
     the bad value: that utterance's cost is +inf and every element of its gradient NaN (exp(... - ll), ll = -inf,
     as the reference's cpu_rnnt.h forms it); the other utterances are exact (no access past a row)."""
     rng = np.random.default_rng(abs(bad) % 97)
