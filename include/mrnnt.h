@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MRNNT_VERSION 12
+#define MRNNT_VERSION 13
 
 /* acts / grads element types */
 #define MRNNT_F32 0
@@ -115,6 +115,28 @@ RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *workspace, const f
 RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, float *costs_dev,
                                void *grads, const float *grad_scale, hipStream_t stream);
 
+/* (version 13) Best path (Viterbi alignment): for every utterance the single most probable monotonic path through
+ * its T_b x (S_b+1) lattice, with the transitions and the band of mrnnt_forward (the alignment band too when
+ * p->alignment restricts the call):
+ *     v(t, s) = max(v(t-1, s) + lpb(t, s), v(t-1, s-1) + lpe(t, s-1)),   v(-1, s) = [s == 0 ? 0 : -inf]
+ * in fp64. Tie rule (part of the contract, the same on both devices): the label arc is taken only when it is
+ * STRICTLY greater than the blank arc; on a tie the frame emits blank.
+ *   alignment_out_dev[b*out_stride + t], t < T_b: labels[b, s] when frame t emits label s, p->blank when it emits
+ *       blank -- the format mrnnt_problem.alignment consumes with align_blank == blank; T_b <= t < out_stride: p->blank.
+ *   costs_dev[b] = -v(T_b-1, S_b) (fp32; may be NULL): the negative log-probability of that one path.
+ * Sentinels: no finite path (masked -inf logits, or a restricting band no path fits): cost +inf and the whole row
+ * (all out_stride entries) -1. A NaN or +inf logit inside the utterance's band: cost NaN and the row -1; the other
+ * utterances are unaffected. Device-resident lengths that fail validation: every cost NaN, every row -1 and
+ * *status_host raised, as mrnnt_forward does.
+ * out_stride >= max_b T_b (host lengths: checked here; lengths_on_device: T_b <= out_stride joins the device
+ * validation). Takes everything mrnnt_forward's log-softmax pass takes (bf16 / fp16 acts, the padded layout, a
+ * restricting alignment with max_shift, device-resident lengths: no host read, capturable). p->alignment and
+ * alignment_out_dev may be the same buffer (the band is built from the input before the output is written).
+ * No new workspace: mrnnt_workspace_size is the size query (the back-pointers, one bit per cell, use the alpha array
+ * of the workspace, so the call overwrites the state of an earlier mrnnt_forward). Asynchronous on `stream`. */
+RNNTStatus mrnnt_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out_dev,
+                       int64_t out_stride, float *costs_dev, hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -172,6 +194,11 @@ RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *workspace, con
 /* mrnnt_read_state for the host implementation (host buffers). */
 RNNTStatus mrnnt_cpu_read_state(const mrnnt_problem *p, const void *workspace, float *den, double *alpha,
                                 double *beta);
+
+/* (version 13) mrnnt_align for the host implementation: alignment_out [B, out_stride] and costs (may be NULL) on the
+ * host, mrnnt_cpu_workspace_size bytes of workspace. Same tie rule and sentinels as mrnnt_align. */
+RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out,
+                           int64_t out_stride, float *costs, int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the
@@ -279,7 +306,7 @@ int mrnnt_version(void);
  * recorded events and returns per-kernel totals in ms and launch counts for
  *   [0] band, [1] log-softmax row reduce, [2] alpha/beta DP, [3] logit gradient, [4] setup,
  *   [5] joint forward, [6] joint backward, [7] joint reduce, [8] chase launch (log-softmax + alpha/beta),
- *   [9] joint dpre GEMM (version 10). */
+ *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch counts under [2]. */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

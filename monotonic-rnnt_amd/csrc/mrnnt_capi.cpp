@@ -575,6 +575,78 @@ RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *ws, size_t ws_bytes
     return mrnnt_backward(p, ws, grad_scale, grads, stream);
 }
 
+RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out_dev, int64_t out_stride,
+                       float *costs_dev, hipStream_t stream) {
+    Plan pl;
+    RNNTStatus st = make_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
+    if (out_stride < 1 || (!pl.dyn && out_stride < pl.T_max))
+        return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
+                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
+    if (!ws || ws_bytes < pl.total)
+        return fail(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pl.total) + " bytes");
+    DevProblem d = make_dev(p, pl, ws);
+    char *w = static_cast<char *>(ws);
+    hipError_t e = hipSuccess;
+    // the separate-kernel route of mrnnt_forward: setup, alignment band, log-softmax, then the Viterbi launch in the
+    // recursion's place (no chase, no planning inside the log-softmax launch)
+    if (pl.dyn) {
+        DynSetupArgs a;
+        std::memset(&a, 0, sizeof(a));
+        if ((st = status_device_ptr(p, &a.status_host)) != RNNT_STATUS_SUCCESS) return st;
+        a.T = p->T_dev;
+        a.S = p->S_dev;
+        a.B = pl.B;
+        a.packed = pl.pad_S1 == 0;
+        a.rows = pl.N;
+        a.cols_cap = pl.cols;
+        a.S_cap = pl.S_max;
+        a.T_cap = out_stride;  // T_b <= out_stride joins the device validation
+        if (pl.pad_S1) a.T_cap = std::min<int64_t>(a.T_cap, pl.pad_T);
+        if (p->alignment) a.T_cap = std::min<int64_t>(a.T_cap, p->align_stride);
+        a.S1_cap = pl.pad_S1;
+        a.scatter_above = INT64_MAX;  // no gradient pass follows
+        a.row_off = reinterpret_cast<int64_t *>(w + pl.off_row);
+        a.col_off = reinterpret_cast<int64_t *>(w + pl.off_col);
+        a.col_b = reinterpret_cast<int *>(w + pl.off_colb);
+        a.lp = d.lp;
+        a.dyn = d.dyn;
+        e = timed(K_SETUP, stream, [&] { return launch_setup_dyn(a, stream); });
+        if (e != hipSuccess) return fail_hip(e, "device-lengths setup kernel");
+    } else if (!p->lattice) {
+        e = timed(K_SETUP, stream, [&] {
+            return launch_setup(p->T_dev, p->S_dev, pl.B, reinterpret_cast<int64_t *>(w + pl.off_row),
+                                reinterpret_cast<int64_t *>(w + pl.off_col),
+                                reinterpret_cast<int *>(w + pl.off_colb), nullptr, 0, stream);
+        });
+        if (e != hipSuccess) return fail_hip(e, "setup kernel");
+    }
+    if (pl.align) {
+        e = timed(K_BAND, stream, [&] {
+            return launch_align(d, p->alignment, p->align_stride, p->align_blank, p->max_shift,
+                                reinterpret_cast<int *>(w + pl.off_mtmp), reinterpret_cast<int *>(w + pl.off_min),
+                                reinterpret_cast<int *>(w + pl.off_max), stream);
+        });
+        if (e != hipSuccess) return fail_hip(e, "alignment band kernels");
+    }
+    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
+    DevProblem ds = d;  // the log-softmax launch's view, as mrnnt_forward's
+    ds.col_mul = column_order(pl, 1);
+    if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {
+        grid = streaming_grid(pl.cols, kStealGridPerCU);
+        ds.steal = grid < pl.cols;
+    }
+    e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
+    // p->alignment may be alignment_out_dev itself: the band kernels above have consumed it (stream order) and the
+    // Viterbi launch reads only the band arrays
+    e = timed(K_DP, stream, [&] { return launch_viterbi(d, pl.S_max, alignment_out_dev, out_stride, costs_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,
                              hipStream_t stream) {
     Plan pl;

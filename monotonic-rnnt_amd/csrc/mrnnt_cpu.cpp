@@ -386,6 +386,57 @@ double beta_utt(const CpuPlan &pl, const Views &w, int b, int T, int S) {
     return Bt[0];
 }
 
+// Best path of one utterance (mrnnt_cpu_align; the HIP path's mrnnt_viterbi.hip): the max-plus recursion
+//   v(t, s) = max(v(t-1, s) + lpb(t, s), v(t-1, s-1) + lpe(t, s-1)) on alpha's band, fp64, two rolling rows,
+// the label arc taken only when strictly greater than the blank arc (a NaN arc makes the cell NaN), one back-pointer
+// byte per cell in the workspace's beta array (unused by this call), then the backtrace from (T-1, S).
+// Writes row[0, out_stride): labels / blank for t < T, blank for t >= T; all -1 when v(T-1, S) is not finite.
+double viterbi_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int b, int *row, int64_t out_stride) {
+    const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+    const int64_t r0 = pl.row_off[b], c0 = pl.col_off[b];
+    unsigned char *bp = reinterpret_cast<unsigned char *>(w.beta + r0);  // [T, W]
+    std::vector<double> va(W, kNegInf), vb(W, kNegInf);
+    double *prev = va.data(), *cur = vb.data();
+    prev[0] = 0.0;  // v(-1, s)
+    for (int t = 0; t < T; ++t) {
+        int lo = std::max(0, t - (T - 1 - S)), hi = std::min(S, t + 1);
+        if (w.min_s) {
+            lo = std::max(lo, w.min_s[c0 + t]);
+            hi = std::min(hi, w.max_s[c0 + t]);
+        }
+        const double *pb = w.lpb + r0 + (int64_t)t * W;
+        const double *pe = w.lpe + r0 + (int64_t)t * W;
+        unsigned char *bt = bp + (int64_t)t * W;
+        for (int s = 0; s < W; ++s) {
+            if (s < lo || s > hi) {
+                cur[s] = kNegInf;
+                bt[s] = 0;
+                continue;
+            }
+            const double x = prev[s] + pb[s];
+            const double y = (s == 0) ? kNegInf : prev[s - 1] + pe[s - 1];
+            const bool take = y > x || y != y;
+            cur[s] = take ? y : x;
+            bt[s] = take ? 1 : 0;
+        }
+        std::swap(prev, cur);
+    }
+    const double fin = prev[S];
+    if (!std::isfinite(fin)) {
+        std::fill(row, row + out_stride, -1);
+        return fin;
+    }
+    const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+    int s = S;
+    for (int t = T - 1; t >= 0; --t) {
+        const int bit = (s > 0 && bp[(int64_t)t * W + s]) ? 1 : 0;
+        row[t] = bit ? lab[s - 1] : p->blank;
+        s -= bit;
+    }
+    std::fill(row + T, row + out_stride, p->blank);
+    return fin;
+}
+
 // Gradient of one lattice column (b, t), every row s in [0, S] (cpu_rnnt.h:216-249):
 //   g[v] = e^(z[v] + den + alpha(t-1,s) + beta(t,s) - ll) - [v == blank] e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll)
 //          - [v == label(s), label != blank] e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll),
@@ -472,6 +523,31 @@ RNNTStatus mrnnt_cpu_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, 
         } else {
             w.llb[b] = beta_utt(pl, w, b, T, S);
         }
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out, int64_t out_stride,
+                           float *costs, int num_threads) {
+    CpuPlan pl;
+    RNNTStatus st = make_cpu_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (!alignment_out) return set_error(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
+    if (out_stride < pl.T_max)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
+                                                        " < max input length " + std::to_string(pl.T_max));
+    if ((st = check_inputs(p, pl)) != RNNT_STATUS_SUCCESS) return st;
+    if (!ws || ws_bytes < pl.total)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pl.total) + " bytes");
+    const Views w = views(pl, ws);
+    const int nt = threads_of(num_threads);
+    // p->alignment may be alignment_out itself: the band is built from it before any row is written
+    if (pl.align) build_band(p, pl, w, nt);
+    softmax_pass(p, pl, w, nt);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int b = 0; b < pl.B; ++b) {
+        const double fin = viterbi_utt(p, pl, w, b, alignment_out + (int64_t)b * out_stride, out_stride);
+        if (costs) costs[b] = (float)(-fin);
     }
     return RNNT_STATUS_SUCCESS;
 }

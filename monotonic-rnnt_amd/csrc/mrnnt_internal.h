@@ -256,6 +256,10 @@ hipError_t launch_mask_state(const DevProblem &p, double *alpha, double *beta, h
 // the reference manager's view: fp32 alpha / beta (band-masked) and log-likelihoods (any may be null)
 hipError_t launch_state_f32(const DevProblem &p, float *alpha, float *beta, float *ll, float *llb, hipStream_t stream);
 hipError_t launch_dp(const DevProblem &p, int S_max, int with_beta, float *costs, hipStream_t stream);
+// mrnnt_align (mrnnt_viterbi.hip): max-plus recursion + backtrace, one workgroup per utterance. Its back-pointer bits
+// go into p.alpha (the call computes no alpha); out: [B, out_stride] alignment rows, costs may be null.
+hipError_t launch_viterbi(const DevProblem &p, int S_max, int *out, int64_t out_stride, float *costs,
+                          hipStream_t stream);
 
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that

@@ -149,6 +149,8 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_cpu_workspace_size": (i, [P, ctypes.POINTER(sz)]),
         "mrnnt_cpu_forward": (i, [P, vp, sz, vp, i, i]),
         "mrnnt_cpu_backward": (i, [P, vp, vp, vp, i]),
+        "mrnnt_align": (i, [P, vp, sz, vp, i64, vp, vp]),
+        "mrnnt_cpu_align": (i, [P, vp, sz, vp, i64, vp, i]),
         "mrnnt_joint_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_forward": (i, [JP, vp, sz, vp, i, vp]),
         "mrnnt_joint_live_rows": (i, [JP, vp, vp, vp]),
@@ -180,8 +182,8 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
             raise ImportError(f"{path} does not export {name}")
         fn.restype = res
         fn.argtypes = args
-    if lib.mrnnt_version() < 12:
-        raise ImportError(f"{path} is a stale build (ABI version {lib.mrnnt_version()} < 12); "
+    if lib.mrnnt_version() < 13:
+        raise ImportError(f"{path} is a stale build (ABI version {lib.mrnnt_version()} < 13); "
                           "rebuild with `make -C monotonic-rnnt_amd`")
     return lib
 

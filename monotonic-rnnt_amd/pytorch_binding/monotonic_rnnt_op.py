@@ -415,6 +415,59 @@ def monotonic_rnnt_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths:
     return result
 
 
+def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                         label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
+                         max_distance_from_alignment: int = 0, blank_label: int = 0,
+                         max_input_length: Optional[int] = None):
+    """Best-path (Viterbi) alignment of every utterance: the single most probable monotonic path through the lattice
+    the loss sums over (mrnnt_align / mrnnt_cpu_align, include/mrnnt.h). Arguments as monotonic_rnnt_loss; an
+    `alignment` with `max_distance_from_alignment` restricts the search to the same band as the loss.
+
+    Returns (alignment, costs):
+        alignment: int32 [B, L] on acts.device. Row b holds, for t < T_b, the label frame t emits or blank_label --
+                   the format `alignment=` of the loss consumes -- and blank_label for t >= T_b.
+        costs:     float32 [B], the negative log-probability of that path (>= the loss of the same inputs).
+    L is max T_b for host lengths, acts.size(1) for padded 4-D acts; for GPU-resident lengths with packed acts pass
+    max_input_length (>= every T_b), or else alignment.size(1) is used when a restricting alignment is given.
+    On a tie the frame emits blank (the label arc is taken only when strictly more probable). An utterance without a
+    finite path (masked -inf logits, a band no path fits) has cost +inf and its row -1; a NaN / +inf logit in its band
+    gives cost NaN and the row -1. Not differentiable: requires_grad is ignored and plain tensors are returned.
+    GPU-resident lengths that fail validation surface through check_lengths() exactly as for the loss."""
+    acts = acts.detach()
+    prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
+    if max_input_length is not None:
+        L = int(max_input_length)
+    elif prep.acts.dim() == 4:
+        L = prep.acts.size(1)
+    elif not prep.dyn:
+        L = int(prep.T_host.max())
+    elif prep.alignment is not None:
+        L = prep.alignment.size(1)
+    else:
+        raise RuntimeError("monotonic_rnnt_align: with GPU-resident lengths and packed acts the longest input length "
+                           "is not known on the host; pass max_input_length (>= every input length)")
+    if L < 1:
+        raise RuntimeError(f"monotonic_rnnt_align: max_input_length must be >= 1, got {L}")
+    lib = _L.load()
+    ws = prep.workspace()
+    B = prep.problem.B
+    out = torch.empty((B, L), dtype=torch.int32, device=prep.device)
+    costs = torch.empty(B, dtype=torch.float32, device=prep.device)
+    if not prep.on_gpu:
+        _L.check(lib.mrnnt_cpu_align(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs),
+                                     prep.num_threads), "mrnnt_cpu_align")
+        return out, costs
+    if prep.dyn:
+        check_lengths(sync=False)  # an earlier call's failed validation surfaces here (no wait)
+    with _on_device(prep.device):
+        _L.check(lib.mrnnt_align(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs),
+                                 prep.stream()), "mrnnt_align")
+        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(prep.device).synchronize()
+            check_lengths(sync=False)
+    return out, costs
+
+
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
@@ -484,4 +537,5 @@ class _Ext:
 
 monotonic_rnnt_cpp = _Ext()
 
-__all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths"]
+__all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
+           "monotonic_rnnt_align"]
