@@ -137,6 +137,36 @@ RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *workspace, size_t w
 RNNTStatus mrnnt_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out_dev,
                        int64_t out_stride, float *costs_dev, hipStream_t stream);
 
+/* Arc posteriors of the lattice, read out of the workspace after mrnnt_forward(with_beta = 1) on the same workspace
+ * and inputs (an addition to version 13: MRNNT_VERSION and every struct are unchanged, so callers that may meet an
+ * older build of version 13 probe for the symbols mrnnt_posteriors / mrnnt_cpu_posteriors). With alpha(t, s) the state
+ * after frame t (alpha(-1, s) = [s == 0 ? 0 : -inf]), beta(t, s) the state before frame t (beta(T, s) = [s == S ? 0 :
+ * -inf]) and ll = alpha(T-1, S), for lattice row (b, t, s):
+ *     blank_post(t, s) = exp(alpha(t-1, s) + lpb(t, s) + beta(t+1, s)   - ll)   P(frame t takes the blank arc out of (t, s))
+ *     label_post(t, s) = exp(alpha(t-1, s) + lpe(t, s) + beta(t+1, s+1) - ll)   (s < S_b; 0 at s = S_b)
+ *     emit(b, t)       = sum_s label_post(t, s)                                 P(frame t emits a label)
+ *     label_time(b, s) = sum_t t * label_post(t, s)   (s < S_b)                 expected frame at which label s is emitted
+ * formed in fp64 from the fp64 state and stored as fp32 -- the two per-row coefficients of the logit gradient. With a
+ * restricting alignment they are the posteriors of the restricted distribution. For every frame sum_s (blank_post +
+ * label_post) = 1, for every label sum_t label_post = 1, and sum_t emit = S_b.
+ *   blank_post_dev / label_post_dev: one value per row of acts, in acts' row layout like grads (packed [N]; padded
+ *       [B, pad_T, pad_S1], padding rows 0), so the host can size them even with lengths_on_device.
+ *   emit_dev [B, emit_stride]: 0 for t >= T_b.      label_time_dev [B, time_stride]: -1 for s >= S_b.
+ *   Any output may be NULL (its work is skipped).
+ * Unreachable rows (alpha(t-1, s) or beta(t, s) = -inf: outside the monotonic band or a restricting alignment band,
+ * masked logits) are exactly 0. An utterance whose ll is not finite (no path: cost +inf; a NaN / +inf logit in its band)
+ * has every per-row value, emit(b, t < T_b) and label_time(b, s < S_b) NaN; the other utterances are unaffected.
+ * Strides: host lengths -- emit_stride >= max T_b and time_stride >= max S_b are checked here, with the NULL
+ * workspace, before any device call (RNNT_STATUS_INVALID_VALUE). lengths_on_device -- nothing is written past a
+ * stride: an utterance with T_b > emit_stride (S_b > time_stride) gets its emit (label_time) row NaN and *status_host
+ * is raised; lengths that failed the forward's validation make every output element, as the host sized it, NaN.
+ * Every sum has a fixed order with fp64 accumulation (bitwise reproducible). Reads the workspace only (not acts, not
+ * labels); no new workspace and no size query; no host read, capturable; asynchronous on `stream`. Its launch counts
+ * under [2] of mrnnt_profile_read. */
+RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *workspace, float *blank_post_dev, float *label_post_dev,
+                            float *emit_dev, int64_t emit_stride, float *label_time_dev, int64_t time_stride,
+                            hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -199,6 +229,12 @@ RNNTStatus mrnnt_cpu_read_state(const mrnnt_problem *p, const void *workspace, f
  * host, mrnnt_cpu_workspace_size bytes of workspace. Same tie rule and sentinels as mrnnt_align. */
 RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out,
                            int64_t out_stride, float *costs, int num_threads);
+
+/* mrnnt_posteriors for the host implementation, after mrnnt_cpu_forward(with_beta = 1) on the same workspace: host
+ * buffers, the same values, rules and stride checks (sums in index order, fp64). */
+RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *workspace, float *blank_post, float *label_post,
+                                float *emit, int64_t emit_stride, float *label_time, int64_t time_stride,
+                                int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the
@@ -306,7 +342,7 @@ int mrnnt_version(void);
  * recorded events and returns per-kernel totals in ms and launch counts for
  *   [0] band, [1] log-softmax row reduce, [2] alpha/beta DP, [3] logit gradient, [4] setup,
  *   [5] joint forward, [6] joint backward, [7] joint reduce, [8] chase launch (log-softmax + alpha/beta),
- *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch counts under [2]. */
+ *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch and mrnnt_posteriors count under [2]. */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

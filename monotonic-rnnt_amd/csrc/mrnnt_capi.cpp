@@ -647,6 +647,30 @@ RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *a
     return RNNT_STATUS_SUCCESS;
 }
 
+RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *ws, float *blank_post_dev, float *label_post_dev,
+                            float *emit_dev, int64_t emit_stride, float *label_time_dev, int64_t time_stride,
+                            hipStream_t stream) {
+    Plan pl;
+    RNNTStatus st = make_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    // with device lengths the kernels bound every write by the strides instead (and raise the status word)
+    if (emit_dev && (emit_stride < 0 || (!pl.dyn && emit_stride < pl.T_max)))
+        return fail(RNNT_STATUS_INVALID_VALUE, "emit row stride " + std::to_string(emit_stride) +
+                                                   " < max input length " + std::to_string(pl.dyn ? 0 : pl.T_max));
+    if (label_time_dev && (time_stride < 0 || (!pl.dyn && time_stride < pl.S_max)))
+        return fail(RNNT_STATUS_INVALID_VALUE, "label_time row stride " + std::to_string(time_stride) +
+                                                   " < max label length " + std::to_string(pl.dyn ? 0 : pl.S_max));
+    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (!p->T_dev || !p->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
+    DevProblem d = make_dev(p, pl, ws);  // acts and labels are never read
+    if (pl.dyn && (st = status_device_ptr(p, &d.status_host)) != RNNT_STATUS_SUCCESS) return st;
+    const PosteriorArgs a{blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride};
+    const int grid = streaming_grid((pl.cols + 15) / 16, 8);  // column workgroups: 16 waves, one column per wave
+    const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "posterior kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,
                              hipStream_t stream) {
     Plan pl;

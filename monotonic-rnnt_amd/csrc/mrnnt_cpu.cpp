@@ -483,6 +483,28 @@ void grad_column(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, cons
     }
 }
 
+// Arc posteriors of row (t, s) inside the monotonic band (mrnnt_cpu_posteriors; the HIP path's row_post,
+// mrnnt_posterior.hip): the blank and label corrections of grad_column in fp64,
+//   bp = e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll),  ep = e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll)  (0 at s = S).
+// An unreachable row (alpha(t-1,s) or beta(t,s) = -inf) is exactly 0, decided before lp is read.
+inline void row_posteriors(const CpuPlan &pl, const Views &w, int b, int t, int T, int S, int s, double ll, double *bp,
+                           double *ep) {
+    const int W = S + 1;
+    const double *A = w.alpha + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
+    *bp = *ep = 0.0;
+    const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s];
+    const double b0 = Bt[(int64_t)t * W + s];
+    if (am == kNegInf || b0 == kNegInf) return;
+    const int64_t r = pl.row_off[b] + (int64_t)t * W + s;
+    const double base = am - ll;
+    const double b1 = (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s];
+    *bp = std::exp(w.lpb[r] + base + b1);
+    if (s < S) {
+        const double b2 = (t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1];
+        *ep = std::exp(w.lpe[r] + base + b2);
+    }
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -577,6 +599,78 @@ RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *ws, const floa
             float *g = grads + (pc * pl.pad_S1 + s0) * V;
             std::fill(g, g + (pl.pad_S1 - s0) * V, 0.0f);
         }
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *blank_post, float *label_post, float *emit,
+                                int64_t emit_stride, float *label_time, int64_t time_stride, int num_threads) {
+    CpuPlan pl;
+    RNNTStatus st = make_cpu_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (emit && emit_stride < pl.T_max)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "emit row stride " + std::to_string(emit_stride) +
+                                                        " < max input length " + std::to_string(pl.T_max));
+    if (label_time && time_stride < pl.S_max)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "label_time row stride " + std::to_string(time_stride) +
+                                                        " < max label length " + std::to_string(pl.S_max));
+    if (!ws) return set_error(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    const Views w = views(pl, const_cast<void *>(ws));
+    const int nt = threads_of(num_threads);
+    constexpr float nan = std::numeric_limits<float>::quiet_NaN();
+    if (blank_post || label_post || emit) {
+#pragma omp parallel for schedule(dynamic, 16) num_threads(nt)
+        for (int64_t c = 0; c < pl.cols; ++c) {
+            const int b = col_utt(pl, c);
+            const int t = (int)(c - pl.col_off[b]);
+            const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+            const double ll = w.ll[b];
+            const bool fin = std::isfinite(ll);
+            const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
+            const int64_t a0 = acts_row(pl, b, t, W);
+            double sum = 0.0;
+            for (int s = 0; s < W; ++s) {
+                double bp = 0.0, ep = 0.0;
+                if (fin && s >= lo && s <= hi) row_posteriors(pl, w, b, t, T, S, s, ll, &bp, &ep);
+                if (blank_post) blank_post[a0 + s] = fin ? (float)bp : nan;
+                if (label_post) label_post[a0 + s] = fin ? (float)ep : nan;
+                sum += ep;
+            }
+            if (emit) emit[(int64_t)b * emit_stride + t] = fin ? (float)sum : nan;
+        }
+    }
+    if (emit)
+        for (int b = 0; b < pl.B; ++b)
+            std::fill(emit + (int64_t)b * emit_stride + p->T_host[b], emit + (int64_t)(b + 1) * emit_stride, 0.0f);
+    if (pl.pad_S1 && (blank_post || label_post)) {  // padding rows of the padded layout: 0
+#pragma omp parallel for schedule(static) num_threads(nt)
+        for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
+            const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
+            const int64_t s0 = t < p->T_host[b] ? p->S_host[b] + 1 : 0;
+            for (float *out : {blank_post, label_post})
+                if (out) std::fill(out + pc * pl.pad_S1 + s0, out + (pc + 1) * pl.pad_S1, 0.0f);
+        }
+    }
+    if (label_time) {
+        std::vector<int64_t> lab_off(pl.B + 1, 0);  // (utterance, label) pairs, one sum along t each
+        for (int b = 0; b < pl.B; ++b) lab_off[b + 1] = lab_off[b] + p->S_host[b];
+#pragma omp parallel for schedule(dynamic, 8) num_threads(nt)
+        for (int64_t i = 0; i < lab_off[pl.B]; ++i) {
+            const int b = (int)(std::upper_bound(lab_off.begin(), lab_off.end(), i) - lab_off.begin()) - 1;
+            const int s = (int)(i - lab_off[b]);
+            const int T = p->T_host[b], S = p->S_host[b];
+            const double ll = w.ll[b];
+            double sum = 0.0;
+            for (int t = s; t <= s + (T - S); ++t) {  // the frames with (t, s) inside the band
+                double bp, ep;
+                row_posteriors(pl, w, b, t, T, S, s, ll, &bp, &ep);
+                sum += (double)t * ep;
+            }
+            label_time[(int64_t)b * time_stride + s] = std::isfinite(ll) ? (float)sum : nan;
+        }
+        for (int b = 0; b < pl.B; ++b)
+            std::fill(label_time + (int64_t)b * time_stride + p->S_host[b], label_time + (int64_t)(b + 1) * time_stride,
+                      -1.0f);
     }
     return RNNT_STATUS_SUCCESS;
 }

@@ -261,6 +261,19 @@ hipError_t launch_dp(const DevProblem &p, int S_max, int with_beta, float *costs
 hipError_t launch_viterbi(const DevProblem &p, int S_max, int *out, int64_t out_stride, float *costs,
                           hipStream_t stream);
 
+// mrnnt_posteriors (mrnnt_posterior.hip): arc posteriors read out of the workspace of a forward with beta. blank /
+// label: one fp32 per acts row in the layout of acts; emit [B, emit_stride]; ltime [B, time_stride]; any may be null.
+struct PosteriorArgs {
+    float *blank;
+    float *label;
+    float *emit;
+    int64_t emit_stride;
+    float *ltime;
+    int64_t time_stride;
+};
+// one launch; col_blocks: its column workgroups (16 waves, one lattice column per wave, grid-stride)
+hipError_t launch_posteriors(const DevProblem &p, const PosteriorArgs &a, int col_blocks, hipStream_t stream);
+
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that
 // published it (never cleared: every launch derives a tag of its own from its dispatch id).

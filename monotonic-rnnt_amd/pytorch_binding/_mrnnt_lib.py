@@ -151,6 +151,8 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_cpu_backward": (i, [P, vp, vp, vp, i]),
         "mrnnt_align": (i, [P, vp, sz, vp, i64, vp, vp]),
         "mrnnt_cpu_align": (i, [P, vp, sz, vp, i64, vp, i]),
+        "mrnnt_posteriors": (i, [P, vp, vp, vp, vp, i64, vp, i64, vp]),
+        "mrnnt_cpu_posteriors": (i, [P, vp, vp, vp, vp, i64, vp, i64, i]),
         "mrnnt_joint_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_forward": (i, [JP, vp, sz, vp, i, vp]),
         "mrnnt_joint_live_rows": (i, [JP, vp, vp, vp]),

@@ -36,6 +36,7 @@ synchronously instead. Host (CPU) lengths plan the launch exactly, uploaded once
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
 from typing import Optional
@@ -468,6 +469,68 @@ def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths
     return out, costs
 
 
+Posteriors = collections.namedtuple("Posteriors", ["blank", "label", "emit", "label_time", "costs"])
+
+
+def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                              label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
+                              max_distance_from_alignment: int = 0, blank_label: int = 0,
+                              max_input_length: Optional[int] = None) -> Posteriors:
+    """Arc posteriors of the lattice the loss sums over -- the soft alignment (mrnnt_posteriors /
+    mrnnt_cpu_posteriors, include/mrnnt.h): the forward pass with beta, then a read-out of its workspace on the same
+    stream. Arguments as monotonic_rnnt_loss; with `alignment` and `max_distance_from_alignment` the posteriors are
+    those of the restricted distribution.
+
+    Returns the namedtuple (blank, label, emit, label_time, costs), all float32 on acts.device:
+        blank, label: shape acts.shape[:-1]. For lattice row (b, t, s) the probability, under the model and given the
+                      labels, that frame t takes the blank arc / the label arc out of state (t, s) (label: 0 at
+                      s = S_b). Per frame, sum_s (blank + label) = 1. Padding rows of 4-D acts are 0.
+        emit:         [B, L], sum_s label(t, s): the probability that frame t emits a label; 0 for t >= T_b.
+                      sum_t emit = S_b. L is chosen as monotonic_rnnt_align chooses it: max T_b for host lengths,
+                      acts.size(1) for padded 4-D acts, else max_input_length (>= every T_b) or alignment.size(1).
+        label_time:   [B, labels.size(1)], sum_t t * label(t, s): the expected frame at which label s is emitted
+                      (increasing in s); -1 for s >= S_b.
+        costs:        [B], the loss of the same inputs.
+    Rows no path can reach (outside the band, masked logits) are exactly 0. An utterance without a finite cost (no
+    path: +inf; a NaN / +inf logit in its band) has NaN in all of its values; the other utterances are unaffected.
+    Not differentiable: requires_grad is ignored and plain tensors are returned. GPU-resident lengths that fail
+    validation make every value NaN and surface through check_lengths() exactly as for the loss."""
+    acts = acts.detach()
+    prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
+    if max_input_length is not None:
+        L = int(max_input_length)
+    elif prep.acts.dim() == 4:
+        L = prep.acts.size(1)
+    elif not prep.dyn:
+        L = int(prep.T_host.max())
+    elif prep.alignment is not None:
+        L = prep.alignment.size(1)
+    else:
+        raise RuntimeError("monotonic_rnnt_posteriors: with GPU-resident lengths and packed acts the longest input "
+                           "length is not known on the host; pass max_input_length (>= every input length)")
+    if L < 1:
+        raise RuntimeError(f"monotonic_rnnt_posteriors: max_input_length must be >= 1, got {L}")
+    costs, ws = _forward(prep, with_beta=True)
+    B, dev = prep.problem.B, prep.device
+    Sw = labels.size(1) if labels.dim() == 2 else prep.labels.size(1)
+    blank = torch.empty(prep.acts.shape[:-1], dtype=torch.float32, device=dev)
+    label = torch.empty_like(blank)
+    emit = torch.empty((B, L), dtype=torch.float32, device=dev)
+    label_time = torch.empty((B, Sw), dtype=torch.float32, device=dev)
+    lib = _L.load()
+    if not prep.on_gpu:
+        _L.check(lib.mrnnt_cpu_posteriors(ctypes.byref(prep.problem), _ptr(ws), _ptr(blank), _ptr(label), _ptr(emit), L,
+                                          _ptr(label_time), Sw, prep.num_threads), "mrnnt_cpu_posteriors")
+        return Posteriors(blank, label, emit, label_time, costs)
+    with _on_device(dev):
+        _L.check(lib.mrnnt_posteriors(ctypes.byref(prep.problem), _ptr(ws), _ptr(blank), _ptr(label), _ptr(emit), L,
+                                      _ptr(label_time), Sw, prep.stream()), "mrnnt_posteriors")
+        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(dev).synchronize()
+            check_lengths(sync=False)
+    return Posteriors(blank, label, emit, label_time, costs)
+
+
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
@@ -538,4 +601,4 @@ class _Ext:
 monotonic_rnnt_cpp = _Ext()
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
-           "monotonic_rnnt_align"]
+           "monotonic_rnnt_align", "monotonic_rnnt_posteriors"]
