@@ -2,7 +2,7 @@
 // (mrnnt_last_error, mrnnt::set_error), mrnnt_version, the host lattice builder (mrnnt_lattice_bytes / _host) and the
 // reference's entry point compute_rnnt_loss (reference src/rnnt_entrypoint.cpp:16-48), which dispatches on
 // options.loc: RNNT_CPU to the CPU computer (mrnnt_cpu.cpp) here, RNNT_GPU to mrnnt::gpu_compute_rnnt_loss in
-// mrnnt_capi.cpp. Kept free of HIP so that the sanitizer build (`make -C monotonic-rnnt_amd asan`) runs this file
+// mrnnt_manager.cpp. Kept free of HIP so that the sanitizer build (`make -C monotonic-rnnt_amd asan`) runs this file
 // with the CPU implementation under AddressSanitizer / UBSan on a host without a GPU.
 #include <cstdint>
 #include <cstring>
@@ -28,7 +28,7 @@ RNNTStatus mrnnt::set_error(RNNTStatus st, const std::string &msg) {
     return st;
 }
 
-// The product library links mrnnt_capi.cpp's definition; this weak one is what a host-only build (the sanitizer
+// The product library links mrnnt_manager.cpp's definition; this weak one is what a host-only build (the sanitizer
 // targets) links instead, and it says so rather than pretending to compute.
 __attribute__((weak)) RNNTStatus mrnnt::gpu_compute_rnnt_loss(RNNTWorkspaceManager &, RNNTOptions, float *, float *) {
     return set_error(RNNT_STATUS_EXECUTION_FAILED, "this is a host-only build of the library: no RNNT_GPU path");

@@ -1,6 +1,6 @@
-// mrnnt_host.h -- declarations shared by the host translation units of libmonotonic_rnnt_amd.so: the HIP
-// side (mrnnt_capi.cpp, hipcc), the host-only C ABI (mrnnt_entry.cpp, g++) and the CPU implementation (mrnnt_cpu.cpp,
-// g++). Plain C++, no HIP types.
+// mrnnt_host.h -- declarations shared by the host translation units of libmonotonic_rnnt_amd.so: the HIP side
+// (hipcc: mrnnt_plan.h and the units that include it), the host-only C ABI (mrnnt_entry.cpp, g++) and the CPU
+// implementation (mrnnt_cpu.cpp, g++). Plain C++, no HIP types.
 // Not installed; not part of the ABI.
 #pragma once
 
@@ -15,7 +15,7 @@ namespace mrnnt {
 // Record `msg` as this thread's mrnnt_last_error() and return `st` (defined in mrnnt_entry.cpp).
 RNNTStatus set_error(RNNTStatus st, const std::string &msg);
 
-// compute_rnnt_loss for loc = RNNT_GPU (mrnnt_capi.cpp; a weak stub in mrnnt_entry.cpp serves host-only builds).
+// compute_rnnt_loss for loc = RNNT_GPU (mrnnt_manager.cpp; a weak stub in mrnnt_entry.cpp serves host-only builds).
 RNNTStatus gpu_compute_rnnt_loss(RNNTWorkspaceManager &workspace_manager, RNNTOptions options, float *costs,
                                  float *gradients);
 

@@ -1,5 +1,5 @@
 // mrnnt_internal.h -- device problem descriptor, launch knobs and kernel launchers shared by the host
-// code (mrnnt_capi.cpp) and the kernels (mrnnt_*.hip). Not installed; not part of the ABI.
+// code (mrnnt_plan.h: host only) and the kernels (mrnnt_*.hip). Not installed; not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,0 +1,299 @@
+// mrnnt_joint_capi.cpp -- the fused joint network + loss ABI of libmonotonic_rnnt_amd.so (mrnnt_joint_* in
+// include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint.hip,
+// mrnnt_joint_gemm.hip). Asynchronous on the caller's stream, no host synchronisation.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#pragma GCC visibility push(default)
+#include "mrnnt.h"
+#pragma GCC visibility pop
+#include "mrnnt_plan.h"
+
+using namespace mrnnt;
+
+namespace {
+
+struct JointPlan {
+    Plan base;
+    int64_t n_inband = 0;
+    size_t off_cnt = 0, off_lcol = 0, off_ls = 0, off_total = 0, off_wplain = 0, off_dbias = 0, total = 0;
+};
+
+mrnnt_problem base_problem(const mrnnt_joint_problem *jp) {
+    mrnnt_problem p;
+    std::memset(&p, 0, sizeof(p));
+    p.B = jp->B;
+    p.V = jp->V;
+    p.blank = jp->blank;
+    p.T_host = jp->T_host;
+    p.S_host = jp->S_host;
+    p.T_dev = jp->T_dev;
+    p.S_dev = jp->S_dev;
+    p.acts = jp->enc;  // the lattice kernels never read acts on this path
+    p.labels = jp->labels;
+    p.label_stride = jp->label_stride;
+    p.alignment = jp->alignment;
+    p.align_stride = jp->align_stride;
+    p.align_blank = jp->align_blank;
+    p.max_shift = jp->max_shift;
+    p.num_rows = -1;
+    return p;
+}
+
+bool aligned16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }
+
+RNNTStatus make_joint_plan(const mrnnt_joint_problem *jp, JointPlan *jl) {
+    if (!jp) return fail(RNNT_STATUS_INVALID_VALUE, "null joint problem");
+    const mrnnt_problem p = base_problem(jp);
+    JointPlan q;
+    RNNTStatus st = make_plan(&p, &q.base);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const int H = jp->H;
+    if (H != 128 && H != 256 && H != 384 && H != 512 && H != 640)
+        return fail(RNNT_STATUS_INVALID_VALUE, "joint H must be 128, 256, 384, 512 or 640 (got " + std::to_string(H) + ")");
+    if (joint_min_lds_bytes(H, jp->V) > 160 * 1024)
+        return fail(RNNT_STATUS_INVALID_VALUE, "V = " + std::to_string(jp->V) + " is too large for the fused joint kernels at H = " +
+                                                   std::to_string(H) + " (weight tiles + bias need " +
+                                                   std::to_string(joint_min_lds_bytes(H, jp->V) / 1024) +
+                                                   " KiB of LDS, 160 KiB per CU); use the unfused loss");
+    if (jp->enc_stride % 8 || jp->pred_stride % 8)
+        return fail(RNNT_STATUS_INVALID_VALUE, "enc/pred utterance strides must be multiples of 8 elements");
+    if (jp->hact_ld != 0 && (jp->hact_ld < H || jp->hact_ld % 8))
+        return fail(RNNT_STATUS_INVALID_VALUE, "hact_ld must be 0 or a multiple of 8 that is >= H");
+    if (jp->enc_stride < (int64_t)q.base.T_max * H || jp->pred_stride < (int64_t)(q.base.S_max + 1) * H)
+        return fail(RNNT_STATUS_INVALID_VALUE, "enc/pred utterance strides smaller than max T * H / (max S + 1) * H");
+    for (int b = 0; b < jp->B; ++b) {
+        const int T = jp->T_host[b], S = jp->S_host[b];
+        for (int t = 0; t < T; ++t) q.n_inband += std::min(t, S) - std::max(0, t - (T - S)) + 1;
+    }
+    size_t o = q.base.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes);
+        return at;
+    };
+    // per-column counts + their exclusive scan, and the scan's tile sums (launch_row_list)
+    q.off_cnt = take(sizeof(int64_t) * (q.base.cols + 2 + (q.base.cols + 1023) / 1024));
+    q.off_lcol = take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
+    q.off_ls = take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
+    q.off_total = take(sizeof(unsigned long long));
+    q.off_wplain = take(sizeof(int));  // the forward's weight-bound flag (launch_joint_wbound)
+    // the gradient pass's per-workgroup dbias column sums (fixed-order reduction), when there is a bias
+    q.off_dbias = (jp->bias && H <= 512) ? take(joint_dbias_part_bytes(std::max<int64_t>(1, q.n_inband), jp->V)) : 0;
+    q.total = o;
+    *jl = q;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus check_joint_pointers(const mrnnt_joint_problem *jp) {
+    if (!jp->enc || !jp->pred || !jp->weight) return fail(RNNT_STATUS_INVALID_VALUE, "enc / pred / weight is null");
+    if (!aligned16(jp->enc) || !aligned16(jp->pred) || !aligned16(jp->weight))
+        return fail(RNNT_STATUS_INVALID_VALUE, "enc / pred / weight must be 16-byte aligned");
+    if (!jp->T_dev || !jp->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
+    if (!jp->labels) return fail(RNNT_STATUS_INVALID_VALUE, "labels is null");
+    return RNNT_STATUS_SUCCESS;
+}
+
+JointArgs joint_args(const mrnnt_joint_problem *jp, const JointPlan &jl, void *ws, int64_t n) {
+    JointArgs j;
+    std::memset(&j, 0, sizeof(j));
+    j.enc = static_cast<const unsigned short *>(jp->enc);
+    j.enc_sb = jp->enc_stride;
+    j.pred = static_cast<const unsigned short *>(jp->pred);
+    j.pred_sb = jp->pred_stride;
+    j.W = static_cast<const unsigned short *>(jp->weight);
+    j.bias = jp->bias;
+    j.H = jp->H;
+    j.hact_ld = jp->hact_ld ? jp->hact_ld : jp->H;
+    j.lcol = carve<int>(ws, jl.off_lcol);
+    j.ls = carve<int>(ws, jl.off_ls);
+    j.n = n;
+    j.opt = kVariants ? tuning().joint_opt : 3;
+    return j;
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_joint_workspace_size(const mrnnt_joint_problem *jp, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    JointPlan jl;
+    const RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = jl.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_row_bound(const mrnnt_joint_problem *jp, int64_t *rows) {
+    if (!rows) return fail(RNNT_STATUS_INVALID_VALUE, "null rows pointer");
+    JointPlan jl;
+    const RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *rows = jl.n_inband;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, float *costs_dev,
+                               int with_beta, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, jl.total)) != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = jl.base;
+    const mrnnt_problem p = base_problem(jp);  // host lengths, no caller lattice: the setup kernel builds the offsets
+    DevProblem d = make_dev(&p, pl, ws);
+    if ((st = prepare_lattice(&p, pl, d, ws, LatticeOpts{}, stream)) != RNNT_STATUS_SUCCESS) return st;
+    // out-of-band lp entries must be finite for the recursion (the acts path zero-fills them in its pass)
+    hipError_t e = launch_zero(carve<char>(ws, pl.off_lp), pl.off_alpha - pl.off_lp, stream);
+    if (e != hipSuccess) return fail_hip(e, "lp zero fill");
+    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
+    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
+                        total, stream);
+    if (e != hipSuccess) return fail_hip(e, "row list kernels");
+    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
+    if (pl.align) j.n_dev = total;  // alignment windows
+    // the weight bound decides the forward's epilogue on the device (no host sync): counted in the forward's time
+    int *wplain = carve<int>(ws, jl.off_wplain);
+    j.wplain = wplain;
+    e = timed(K_JOINT_FWD, stream, [&] {
+        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
+        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    e = timed(K_DP, stream, [&] { return launch_dp(d, pl.S_max, with_beta ? 1 : 0, costs_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "alpha/beta kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *jp, void *ws, unsigned long long *count_dev,
+                                 hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (!ws || !count_dev) return fail(RNNT_STATUS_INVALID_VALUE, "workspace / count is null");
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = make_dev(&p, jl.base, ws);
+    const hipError_t e = launch_row_list(d, 1, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol),
+                                         carve<int>(ws, jl.off_ls), count_dev, stream);
+    if (e != hipSuccess) return fail_hip(e, "live row list kernels");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale,
+                                void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (n_live < 0 || n_live > jl.n_inband)
+        return fail(RNNT_STATUS_INVALID_VALUE, "n_live outside [0, in-band rows]");
+    if (n_live > 0 && (!G || !Hact)) return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact is null");
+    if (n_live > 0 && (!aligned16(G) || !aligned16(Hact)))
+        return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact must be 16-byte aligned");
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = make_dev(&p, jl.base, ws);
+    JointArgs j = joint_args(jp, jl, ws, n_live);
+    j.n_dev = jp->live_count_dev;  // n_live a host bound: workgroups past the device count exit (their rows zeroed below)
+    j.G = static_cast<unsigned short *>(G);
+    j.Hact = static_cast<unsigned short *>(Hact);
+    j.bt_idx = bt_idx;
+    j.bs_idx = bs_idx;
+    j.scale = grad_scale;
+    j.dbias = jp->dbias;
+    if (jp->dbias && jp->H > 512) return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass needs H <= 512");
+    if (jp->dbias && joint_dbias_lds_bytes(jp->H, jp->V) > 160 * 1024)
+        return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass: V too large for its LDS column sums at this H "
+                                               "(sum G's columns outside: dbias = NULL)");
+    if (jp->dbias && !jl.off_dbias)
+        return fail(RNNT_STATUS_INVALID_VALUE, "dbias needs a bias (the workspace holds its partial sums only then)");
+    if (jp->dbias) j.dbias_part = carve<float>(ws, jl.off_dbias);
+    hipError_t e = timed(K_JOINT_BWD, stream, [&] {
+        const hipError_t eb = launch_joint_backward(d, j, stream);
+        if (eb != hipSuccess || !jp->live_count_dev) return eb;
+        return launch_joint_tail_zero(j.G, jp->V, j.Hact, j.hact_ld, n_live, jp->live_count_dev, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint gradient kernel");
+    if (jp->dbias && n_live > 0) {
+        e = launch_joint_dbias_sum(j, jp->V, stream);
+        if (e != hipSuccess) return fail_hip(e, "joint dbias sum kernels");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+// pre: dH already holds dpre (Hact unused; the kRedPre kernel form)
+static RNNTStatus joint_reduce(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const void *dH,
+                               const void *Hact, bool pre, float *d_enc, float *d_pred, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if (!ws || !d_enc || !d_pred) return fail(RNNT_STATUS_INVALID_VALUE, "workspace / d_enc / d_pred is null");
+    if (n_live < 0 || n_live > jl.n_inband) return fail(RNNT_STATUS_INVALID_VALUE, "n_live outside [0, in-band rows]");
+    if (n_live > 0 && (!dH || (reinterpret_cast<uintptr_t>(dH) & 7)))
+        return fail(RNNT_STATUS_INVALID_VALUE, pre ? "dpre null or not 8-byte aligned" : "dH null or not 8-byte aligned");
+    if (!pre && n_live > 0 && (!Hact || (reinterpret_cast<uintptr_t>(Hact) & 7)))
+        return fail(RNNT_STATUS_INVALID_VALUE, "Hact null or not 8-byte aligned (a dH that already holds dpre: "
+                                               "mrnnt_joint_reduce_pre)");
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = make_dev(&p, jl.base, ws);
+    JointArgs j = joint_args(jp, jl, ws, n_live);
+    j.Hact = pre ? nullptr : static_cast<unsigned short *>(const_cast<void *>(Hact));
+    const int64_t *off = carve<int64_t>(ws, jl.off_cnt);
+    const hipError_t e = timed(K_JOINT_RED, stream, [&] {
+        return launch_joint_reduce(d, j, off, jl.base.T_max, jl.base.S_max, static_cast<const unsigned short *>(dH),
+                                   d_enc, d_pred, jp->reduce_scratch, jp->reduce_scratch_bytes, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint reduce kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_reduce(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const void *dH,
+                              const void *Hact, float *d_enc, float *d_pred, hipStream_t stream) {
+    return joint_reduce(jp, ws, n_live, dH, Hact, false, d_enc, d_pred, stream);
+}
+
+RNNTStatus mrnnt_joint_reduce_pre(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const void *dpre,
+                                  float *d_enc, float *d_pred, hipStream_t stream) {
+    return joint_reduce(jp, ws, n_live, dpre, nullptr, true, d_enc, d_pred, stream);
+}
+
+RNNTStatus mrnnt_joint_dpre(const mrnnt_joint_problem *jp, int64_t n_live, const void *G, const void *weight_t,
+                            const void *Hact, void *dpre, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (jp->H != 256 && jp->H != 512)
+        return fail(RNNT_STATUS_INVALID_VALUE, "mrnnt_joint_dpre: H must be 256 or 512 (use a library GEMM)");
+    if (jp->V % 8) return fail(RNNT_STATUS_INVALID_VALUE, "mrnnt_joint_dpre: V must be a multiple of 8");
+    if (n_live < 0 || n_live > jl.n_inband) return fail(RNNT_STATUS_INVALID_VALUE, "n_live outside [0, in-band rows]");
+    const int64_t ld = jp->hact_ld ? jp->hact_ld : jp->H;
+    if (ld < jp->H || ld % 4) return fail(RNNT_STATUS_INVALID_VALUE, "hact_ld must be >= H and a multiple of 4");
+    if (n_live == 0) return RNNT_STATUS_SUCCESS;
+    for (const void *q : {G, weight_t, Hact, static_cast<const void *>(dpre)})
+        if (!q || (reinterpret_cast<uintptr_t>(q) & 15))
+            return fail(RNNT_STATUS_INVALID_VALUE, "mrnnt_joint_dpre: G / weight_t / Hact / dpre null or not 16-byte aligned");
+    const hipError_t e = timed(K_JOINT_DPRE, stream, [&] {
+        return launch_joint_dpre(static_cast<const unsigned short *>(G), static_cast<const unsigned short *>(weight_t),
+                                 static_cast<const unsigned short *>(Hact), ld, static_cast<unsigned short *>(dpre),
+                                 n_live, jp->V, jp->H, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint dpre kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_reduce_scratch_bytes(const mrnnt_joint_problem *jp, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    JointPlan jl;
+    const RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = joint_reduce_scratch_bytes(jl.base.B, jl.base.T_max, jl.base.S_max, jp->H);
+    return RNNT_STATUS_SUCCESS;
+}
+
+}  // extern "C"

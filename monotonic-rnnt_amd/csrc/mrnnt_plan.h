@@ -1,0 +1,105 @@
+// mrnnt_plan.h -- what the host translation units of the GPU path share (mrnnt_capi.cpp: the flat loss ABI,
+// mrnnt_joint_capi.cpp: the fused-joint ABI, mrnnt_manager.cpp: the reference-shaped C++ surface): validation and the
+// workspace plan, the device-problem builder, the lattice preparation, the chase decision, launch grids, the status
+// word and the per-launch profile. Defined in mrnnt_plan.cpp, which holds the one instance of every piece of
+// process-wide state. Host only (the kernels include mrnnt_internal.h alone); hidden visibility; not part of the ABI.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#pragma GCC visibility push(default)
+#include "mrnnt.h"
+#pragma GCC visibility pop
+#include "mrnnt_internal.h"
+
+namespace mrnnt {
+
+// this thread's mrnnt_last_error() (the error state lives in mrnnt_entry.cpp)
+RNNTStatus fail(RNNTStatus st, const std::string &msg);
+RNNTStatus fail_hip(hipError_t e, const char *where);
+
+size_t align_up(size_t x);  // to the workspace's 256-byte granule
+
+// Launch plan of one problem. With host lengths every size is exact. With device-resident lengths
+// (lengths_on_device) the host plans from bounds it knows without a read-back: N = the rows of acts (packed: exact,
+// checked on the device; padded: B*pad_T*pad_S1), cols <= N (packed; every column holds >= 1 row) or B*pad_T
+// (padded), S_max <= label_stride; the setup kernel publishes the real values (DynWords) for the kernels.
+struct Plan {
+    int B = 0, V = 0, S_max = 0, T_max = 0;
+    int64_t N = 0, cols = 0;
+    int elem = ELEM_F32;
+    int64_t pad_T = 0, pad_S1 = 0;
+    bool align = false;
+    bool dyn = false;
+    size_t off_flags = 0, flags_bytes = 0;  // the chase launch's ready flags (8 bytes per column), where it can run
+    size_t off_row, off_col, off_colb, off_mtmp, off_min, off_max, off_den, off_lp, off_alpha, off_beta, off_ll,
+        off_llb, off_dyn, total;
+};
+
+RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl);
+DevProblem make_dev(const mrnnt_problem *p, const Plan &pl, const void *ws);
+
+// The array at byte offset `off` of a workspace.
+template <class T>
+T *carve(void *ws, size_t off) {
+    return reinterpret_cast<T *>(static_cast<char *>(ws) + off);
+}
+
+// "workspace too small" unless ws holds `need` bytes
+RNNTStatus check_workspace(const void *ws, size_t ws_bytes, size_t need);
+
+// Lower bound on the column count that the host knows with device lengths: rows / (label stride + 1), exact when
+// every S_b equals the stride, or B * pad_T for the padded layout.
+int64_t min_cols(const Plan &pl);
+
+// The chase launch (mrnnt_chase.hip): whether it pays for this call (the plan holds its ready flags where its shape
+// can take it at all), and a fresh tag per launch.
+bool chase_pays(const Plan &pl, bool with_beta);
+uint64_t chase_epoch();
+
+// Column order of a streaming pass (DevProblem::col_mul): XCD-chunked (< 0), scattered (> 0: with device lengths a
+// marker the kernels replace by the device's multiplier, resolve_dyn) or in order (0). bit: 1 log-softmax, 2 gradient.
+int64_t column_order(const Plan &pl, int bit);
+
+// per_cu workgroups of 4 waves per CU walking `cols` columns grid-stride, never more than the columns; per_cu == 0:
+// one workgroup per column (hardware-scheduled)
+int streaming_grid(int64_t cols, int per_cu);
+
+// Device address of a caller's status word (host-mapped memory), nullptr for none.
+RNNTStatus status_device_ptr(const mrnnt_problem *p, int **dev);
+int *process_status_word();  // mrnnt_status_word(): one host-mapped word per process
+
+// The lattice offsets and the alignment band of a call, in its workspace: exactly one of the device-lengths setup
+// kernel, the host-lengths setup kernel (no caller lattice) or nothing (a caller lattice), then the band kernels when
+// the plan has an alignment. What the entry points do differently is all here:
+struct LatticeOpts {
+    int64_t t_cap = 0;                   // one more bound on T_b for the device validation (0 = none)
+    int64_t scatter_above = INT64_MAX;   // DynSetupArgs::scatter_above (INT64_MAX: no gradient pass follows)
+    bool zero_lp_pads = true;            // device lengths: the setup kernel zeroes the pads of the lp array
+    bool report_status = true;           // device lengths: a failed validation raises the caller's status word
+    bool timed = true;                   // the launches count in the profile (K_SETUP, K_BAND)
+};
+RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProblem &d, void *ws,
+                           const LatticeOpts &o, hipStream_t stream);
+
+// ---- profiling (mrnnt_profile_enable / mrnnt_profile_read) ------------------------------------------------------
+struct ProfRec {
+    int id;
+    hipEvent_t a, b;
+};
+// false when the profile is off (or out of events); else r->a is recorded on s and profile_end records r->b
+bool profile_begin(int id, hipStream_t s, ProfRec *r);
+void profile_end(const ProfRec &r, hipStream_t s);
+
+template <class F>
+hipError_t timed(int id, hipStream_t s, F &&launch) {
+    ProfRec r;
+    if (!profile_begin(id, s, &r)) return launch();
+    const hipError_t e = launch();
+    profile_end(r, s);
+    return e;
+}
+
+}  // namespace mrnnt
