@@ -290,6 +290,40 @@ RNNTStatus mrnnt_joint_row_bound(const mrnnt_joint_problem *p, int64_t *rows);
 RNNTStatus mrnnt_joint_forward(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
                                float *costs_dev, int with_beta, hipStream_t stream);
 
+/* mrnnt_align for the fused joint (an addition to version 13: MRNNT_VERSION and both structs are unchanged, so callers
+ * that may meet an older build of version 13 probe for the symbols mrnnt_joint_align / mrnnt_joint_posteriors): the
+ * best path through the lattice of the logits the joint never stores. Everything mrnnt_joint_forward does up to and
+ * including its joint log-softmax pass (p->alignment / p->max_shift restrict the search as they restrict the loss),
+ * then the Viterbi launch of mrnnt_align in the recursion's place. The contract is mrnnt_align's: the label arc is
+ * taken only when STRICTLY greater than the blank arc; alignment_out_dev[b*out_stride + t] is labels[b, s] or
+ * p->blank for t < T_b (the format p->alignment consumes with align_blank == blank) and p->blank for
+ * T_b <= t < out_stride; costs_dev[b] (fp32, may be NULL) is the negative log-probability of that path. No finite
+ * path: cost +inf and the whole row -1. A NaN or +inf logit inside the utterance's band (e.g. a NaN in its enc rows):
+ * cost NaN and the row -1; the other utterances are bit-identical to a call without it.
+ * alignment_out_dev != NULL and out_stride >= max_b T_b are checked on the host before any device call
+ * (RNNT_STATUS_INVALID_VALUE). p->alignment and alignment_out_dev may be the same buffer (the band is built from the
+ * input before the output is written). Workspace: mrnnt_joint_workspace_size bytes; the back-pointers, one bit per
+ * cell, use its alpha array, so the call OVERWRITES the state of an earlier mrnnt_joint_forward on that workspace (run
+ * the forward again before mrnnt_joint_live_rows / mrnnt_joint_backward / mrnnt_joint_posteriors). The joint launch
+ * counts under [5] of mrnnt_profile_read and the Viterbi launch under [2]. Asynchronous on `stream`, no host read. */
+RNNTStatus mrnnt_joint_align(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                             int *alignment_out_dev, int64_t out_stride, float *costs_dev, hipStream_t stream);
+
+/* mrnnt_posteriors for the fused joint, after mrnnt_joint_forward(with_beta = 1) on the same workspace and inputs:
+ * the same values and rules (fp64 formation, unreachable rows exactly 0, a non-finite ll makes that utterance's
+ * values NaN and no other's, emit 0 for t >= T_b, label_time -1 for s >= S_b, any output may be NULL, every sum in a
+ * fixed order: bitwise reproducible). One difference: a joint caller has no packed row index, so the per-row outputs
+ * lie on the joint's own grid,
+ *   blank_post_dev / label_post_dev: [B, grid_T, grid_S1], row (b, t, s) at (b*grid_T + t)*grid_S1 + s, the rows
+ *       with t >= T_b or s > S_b 0 -- e.g. grid_T / grid_S1 = the frame / label-position slots of enc / pred.
+ * grid_T >= max T_b and grid_S1 >= max S_b + 1 (when either per-row output is given), emit_stride >= max T_b and
+ * time_stride >= max S_b are checked on the host, with the NULL workspace, before any device call
+ * (RNNT_STATUS_INVALID_VALUE). Reads the workspace only; its launch counts under [2] of mrnnt_profile_read.
+ * Asynchronous on `stream`, no host read. */
+RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *p, const void *workspace, float *blank_post_dev,
+                                  float *label_post_dev, int64_t grid_T, int64_t grid_S1, float *emit_dev,
+                                  int64_t emit_stride, float *label_time_dev, int64_t time_stride, hipStream_t stream);
+
 /* After mrnnt_joint_forward(with_beta=1): list the live lattice rows (those with a non-zero fp32 logit
  * gradient) in the workspace and write their number to *count_dev (device uint64). */
 RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *p, void *workspace, unsigned long long *count_dev,

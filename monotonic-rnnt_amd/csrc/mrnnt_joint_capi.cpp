@@ -1,6 +1,7 @@
 // mrnnt_joint_capi.cpp -- the fused joint network + loss ABI of libmonotonic_rnnt_amd.so (mrnnt_joint_* in
 // include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint.hip,
-// mrnnt_joint_gemm.hip). Asynchronous on the caller's stream, no host synchronisation.
+// mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors put the Viterbi launch / the posterior read-out of
+// the loss ABI behind the joint's log-softmax pass. Asynchronous on the caller's stream, no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -115,6 +116,41 @@ JointArgs joint_args(const mrnnt_joint_problem *jp, const JointPlan &jl, void *w
     return j;
 }
 
+// What mrnnt_joint_forward and mrnnt_joint_align share after the plan: pointer and workspace checks, the lattice (and
+// the alignment band), then the joint log-softmax pass that leaves lpb / lpe of every row the recursion can use in the
+// workspace. *out: the device problem for the launch that follows (launch_dp / launch_viterbi).
+RNNTStatus joint_log_softmax(const mrnnt_joint_problem *jp, const JointPlan &jl, void *ws, size_t ws_bytes,
+                             int64_t t_cap, hipStream_t stream, DevProblem *out) {
+    RNNTStatus st = check_joint_pointers(jp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, jl.total)) != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = jl.base;
+    const mrnnt_problem p = base_problem(jp);  // host lengths, no caller lattice: the setup kernel builds the offsets
+    DevProblem d = make_dev(&p, pl, ws);
+    LatticeOpts o;
+    o.t_cap = t_cap;
+    if ((st = prepare_lattice(&p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
+    // out-of-band lp entries must be finite for the recursion (the acts path zero-fills them in its pass)
+    hipError_t e = launch_zero(carve<char>(ws, pl.off_lp), pl.off_alpha - pl.off_lp, stream);
+    if (e != hipSuccess) return fail_hip(e, "lp zero fill");
+    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
+    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
+                        total, stream);
+    if (e != hipSuccess) return fail_hip(e, "row list kernels");
+    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
+    if (pl.align) j.n_dev = total;  // alignment windows
+    // the weight bound decides the forward's epilogue on the device (no host sync): counted in the forward's time
+    int *wplain = carve<int>(ws, jl.off_wplain);
+    j.wplain = wplain;
+    e = timed(K_JOINT_FWD, stream, [&] {
+        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
+        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    *out = d;
+    return RNNT_STATUS_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -142,31 +178,65 @@ RNNTStatus mrnnt_joint_forward(const mrnnt_joint_problem *jp, void *ws, size_t w
     JointPlan jl;
     RNNTStatus st = make_joint_plan(jp, &jl);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
-    if ((st = check_workspace(ws, ws_bytes, jl.total)) != RNNT_STATUS_SUCCESS) return st;
-    const Plan &pl = jl.base;
-    const mrnnt_problem p = base_problem(jp);  // host lengths, no caller lattice: the setup kernel builds the offsets
-    DevProblem d = make_dev(&p, pl, ws);
-    if ((st = prepare_lattice(&p, pl, d, ws, LatticeOpts{}, stream)) != RNNT_STATUS_SUCCESS) return st;
-    // out-of-band lp entries must be finite for the recursion (the acts path zero-fills them in its pass)
-    hipError_t e = launch_zero(carve<char>(ws, pl.off_lp), pl.off_alpha - pl.off_lp, stream);
-    if (e != hipSuccess) return fail_hip(e, "lp zero fill");
-    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
-    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
-                        total, stream);
-    if (e != hipSuccess) return fail_hip(e, "row list kernels");
-    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
-    if (pl.align) j.n_dev = total;  // alignment windows
-    // the weight bound decides the forward's epilogue on the device (no host sync): counted in the forward's time
-    int *wplain = carve<int>(ws, jl.off_wplain);
-    j.wplain = wplain;
-    e = timed(K_JOINT_FWD, stream, [&] {
-        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
-        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
-    e = timed(K_DP, stream, [&] { return launch_dp(d, pl.S_max, with_beta ? 1 : 0, costs_dev, stream); });
+    DevProblem d;
+    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, 0, stream, &d)) != RNNT_STATUS_SUCCESS) return st;
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_dp(d, jl.base.S_max, with_beta ? 1 : 0, costs_dev, stream); });
     if (e != hipSuccess) return fail_hip(e, "alpha/beta kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_align(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, int *alignment_out_dev,
+                             int64_t out_stride, float *costs_dev, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
+    if (out_stride < jl.base.T_max)
+        return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
+                                                   " < max input length " + std::to_string(jl.base.T_max));
+    DevProblem d;
+    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, out_stride, stream, &d)) != RNNT_STATUS_SUCCESS) return st;
+    // jp->alignment may be alignment_out_dev itself: the band kernels have consumed it (stream order), the joint
+    // pass and the Viterbi launch read only the band arrays
+    const hipError_t e = timed(K_DP, stream, [&] {
+        return launch_viterbi(d, jl.base.S_max, alignment_out_dev, out_stride, costs_dev, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws, float *blank_post_dev,
+                                  float *label_post_dev, int64_t grid_T, int64_t grid_S1, float *emit_dev,
+                                  int64_t emit_stride, float *label_time_dev, int64_t time_stride, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = jl.base;
+    if ((blank_post_dev || label_post_dev) && (grid_T < pl.T_max || grid_S1 < (int64_t)pl.S_max + 1))
+        return fail(RNNT_STATUS_INVALID_VALUE, "posterior grid [" + std::to_string(grid_T) + ", " +
+                                                   std::to_string(grid_S1) + "] smaller than [max T, max S + 1] = [" +
+                                                   std::to_string(pl.T_max) + ", " + std::to_string(pl.S_max + 1) + "]");
+    if (emit_dev && emit_stride < pl.T_max)
+        return fail(RNNT_STATUS_INVALID_VALUE, "emit row stride " + std::to_string(emit_stride) +
+                                                   " < max input length " + std::to_string(pl.T_max));
+    if (label_time_dev && time_stride < pl.S_max)
+        return fail(RNNT_STATUS_INVALID_VALUE, "label_time row stride " + std::to_string(time_stride) +
+                                                   " < max label length " + std::to_string(pl.S_max));
+    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (!jp->T_dev || !jp->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = make_dev(&p, pl, ws);
+    // the lattice is packed (state rows row_off[b] + t * (S_b + 1) + s); only the per-row OUTPUTS take the padded
+    // mapping, which the posterior launch keeps apart from the state rows (acts_col_base and its padding fills)
+    if (blank_post_dev || label_post_dev) {
+        d.pad_T = grid_T;
+        d.pad_S1 = grid_S1;
+    }
+    const PosteriorArgs a{blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride};
+    const int grid = streaming_grid((pl.cols + 15) / 16, 8);  // as mrnnt_posteriors
+    const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "posterior kernel");
     return RNNT_STATUS_SUCCESS;
 }
 

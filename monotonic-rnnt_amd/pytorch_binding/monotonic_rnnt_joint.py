@@ -11,9 +11,16 @@ without materialising them: the HIP kernels of `mrnnt_joint.hip` form each tile 
 inside the gradient pass. Backward returns gradients for enc, pred, weight and bias: the fused kernel writes
 the logit gradient G and the activations tanh(enc + pred) of the live rows (bf16); dweight = G^T Hact (split-K
 batched GEMM, fp32 out; Hact carries a ones column when dbias is needed, so dbias = sum G comes out of the same
-GEMM) is a library GEMM over those rows (hipBLASLt through torch); dpre = (G weight) (1 - Hact^2) is one
-hand-written MFMA pass (mrnnt_joint_dpre; H = 256 / 512 -- other widths take dH from hipBLASLt and multiply in the
-reduce), and mrnnt_joint_reduce folds dpre into denc (sum over s) and dpred (sum over t) in one pass.
+GEMM) is a library GEMM over those rows (hipBLASLt through torch); dH = G weight is a library GEMM too by default,
+and mrnnt_joint_reduce multiplies it by (1 - Hact^2) as it folds dpre into denc (sum over s) and dpred (sum over t) in
+one pass. MRNNT_JOINT_DH=mfma (H = 256 / 512, V % 8 == 0) forms dpre in one hand-written MFMA pass instead
+(mrnnt_joint_dpre, then mrnnt_joint_reduce_pre): opt-in while it is slower than the GEMM it replaces.
+
+    alignment, costs = monotonic_rnnt_joint_align(enc, pred, weight, bias, labels, input_lengths, label_lengths)
+    post = monotonic_rnnt_joint_posteriors(enc, pred, weight, bias, labels, input_lengths, label_lengths)
+
+are monotonic_rnnt_align / monotonic_rnnt_posteriors of the same never-stored logits: the joint log-softmax pass, then
+the Viterbi launch in the recursion's place, or the recursion with beta and the posterior read-out.
 
 Shapes: enc [B, T_slots >= max T, H], pred [B, S_slots >= max S + 1, H], weight [V, H] (torch.nn.Linear
 layout), bias [V] or None; H in {128, 256, 384, 512, 640}. Inputs of other floating dtypes are cast to bf16
@@ -31,10 +38,10 @@ import torch
 
 try:
     from . import _mrnnt_lib as _L
-    from .monotonic_rnnt_op import _check_labels, _lengths
+    from .monotonic_rnnt_op import Posteriors, _check_labels, _lengths
 except ImportError:
     import _mrnnt_lib as _L
-    from monotonic_rnnt_op import _check_labels, _lengths
+    from monotonic_rnnt_op import Posteriors, _check_labels, _lengths
 
 _L.load()
 
@@ -113,6 +120,33 @@ class _JointPrepared:
                                              1 if with_beta else 0, self.stream()), "mrnnt_joint_forward")
         return costs, ws
 
+    def align(self, L: int):
+        """(alignment int32 [B, L], costs [B]): mrnnt_joint_align on a workspace of its own."""
+        lib = _L.load()
+        n = ctypes.c_size_t(0)
+        _L.check(lib.mrnnt_joint_workspace_size(ctypes.byref(self.problem), ctypes.byref(n)), "joint_workspace_size")
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            out = torch.empty((self.B, L), dtype=torch.int32, device=self.device)
+            costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
+            _L.check(lib.mrnnt_joint_align(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(out), L, _vp(costs),
+                                           self.stream()), "mrnnt_joint_align")
+        return out, costs
+
+    def posteriors(self, label_width: int) -> Posteriors:
+        """The forward with beta, then mrnnt_joint_posteriors on its workspace (the grid of enc / pred slots)."""
+        costs, ws = self.forward(with_beta=True)
+        Tg, Sg = self.enc.size(1), self.pred.size(1)
+        with torch.cuda.device(self.device):
+            blank = torch.empty((self.B, Tg, Sg), dtype=torch.float32, device=self.device)
+            label = torch.empty_like(blank)
+            emit = torch.empty((self.B, Tg), dtype=torch.float32, device=self.device)
+            label_time = torch.empty((self.B, label_width), dtype=torch.float32, device=self.device)
+            _L.check(_L.load().mrnnt_joint_posteriors(ctypes.byref(self.problem), _vp(ws), _vp(blank), _vp(label), Tg,
+                                                      Sg, _vp(emit), Tg, _vp(label_time), label_width,
+                                                      self.stream()), "mrnnt_joint_posteriors")
+        return Posteriors(blank, label, emit, label_time, costs)
+
     def backward_rows(self, ws, grad_scale, with_index=False, bias_column=False, dbias=None, capturable=False):
         """The fused gradient pass over the live rows: (G [n, V], Hact [n, H]) and, with_index, the enc / pred
         row of each live row (bt_idx, bs_idx). bias_column: Hact is [n, _HACT_LD[H]] with column H = 1 (and zeros
@@ -190,7 +224,7 @@ _BIAS_SUM = os.environ.get("MRNNT_JOINT_BIAS_SUM") == "1"
 _CAPTURABLE = os.environ.get("MRNNT_JOINT_CAPTURABLE") == "1"
 # dH: a library GEMM (hipBLASLt) and the reduce's own multiply by default; MRNNT_JOINT_DH=mfma takes the library's
 # hand-written MFMA kernel with the tanh derivative fused (mrnnt_joint_dpre: H = 256 / 512, V % 8 == 0) -- opt-in
-# while it is slower than the GEMM it replaces (6.1 vs 3.8 ms at H = 512, the reduce 2.7 -> 2.1 ms)
+# while it is slower than the GEMM it replaces (4.84 vs 3.77 ms at H = 512, profiles/r06/final2/dpre_bench.json)
 _DH_BLAS = os.environ.get("MRNNT_JOINT_DH", "blas") != "mfma"
 
 
@@ -320,4 +354,52 @@ def monotonic_rnnt_joint_loss(enc: torch.Tensor, pred: torch.Tensor, weight: tor
                                             capturable)
 
 
-__all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss"]
+def _bf16(x):
+    x = x.detach()
+    return x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+
+
+def monotonic_rnnt_joint_align(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                               bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
+                               label_lengths: torch.Tensor, blank_label: int = 0,
+                               alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
+                               max_input_length: Optional[int] = None):
+    """Best-path (Viterbi) alignment under the joint network tanh(enc + pred) @ weight.T + bias, without materialising
+    its logits (mrnnt_joint_align): monotonic_rnnt_align of the acts monotonic_rnnt_joint_loss never stores. Arguments
+    as monotonic_rnnt_joint_loss; `alignment` with `max_distance_from_alignment` restricts the search to the band the
+    restricted loss sums over.
+
+    Returns (alignment, costs): alignment int32 [B, L], row b the label frame t emits or blank_label for t < T_b and
+    blank_label from T_b on -- what `alignment=` of monotonic_rnnt_joint_loss consumes; costs float32 [B], the negative
+    log-probability of that path (>= the loss). L is max T_b, or max_input_length (>= every T_b) when given.
+    On a tie the frame emits blank. An utterance without a finite path has cost +inf and its row -1; a NaN / +inf logit
+    in its band gives cost NaN and the row -1. Not differentiable: plain tensors are returned."""
+    prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
+                          blank_label, alignment, max_distance_from_alignment)
+    L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
+    if L < 1:
+        raise RuntimeError(f"monotonic_rnnt_joint_align: max_input_length must be >= 1, got {L}")
+    return prep.align(L)
+
+
+def monotonic_rnnt_joint_posteriors(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                                    bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
+                                    label_lengths: torch.Tensor, blank_label: int = 0,
+                                    alignment: Optional[torch.Tensor] = None,
+                                    max_distance_from_alignment: int = 0) -> Posteriors:
+    """Arc posteriors (the soft alignment) under the joint network, without materialising its logits: the fused
+    forward with beta, then mrnnt_joint_posteriors on its workspace. Arguments as monotonic_rnnt_joint_loss; with
+    `alignment` the posteriors are those of the restricted distribution.
+
+    Returns monotonic_rnnt_posteriors' namedtuple (blank, label, emit, label_time, costs), float32, with the per-row
+    values on the joint's own grid: blank, label [B, enc.size(1), pred.size(1)] (row (b, t, s); 0 for t >= T_b or
+    s > S_b), emit [B, enc.size(1)] (0 for t >= T_b), label_time [B, labels.size(1)] (-1 for s >= S_b), costs [B] --
+    bit for bit monotonic_rnnt_joint_loss of the same inputs. Rows no path reaches are exactly 0; an utterance
+    without a finite cost has NaN in its own values only. Not differentiable: plain tensors are returned."""
+    prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
+                          blank_label, alignment, max_distance_from_alignment)
+    return prep.posteriors(labels.size(1) if labels.dim() == 2 else prep.labels.size(1))
+
+
+__all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_joint_align",
+           "monotonic_rnnt_joint_posteriors"]
