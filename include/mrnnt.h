@@ -167,6 +167,39 @@ RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *workspace, float
                             float *emit_dev, int64_t emit_stride, float *label_time_dev, int64_t time_stride,
                             hipStream_t stream);
 
+/* Whole alignments drawn from the path posterior p(path | labels, acts), read out of the workspace after
+ * mrnnt_forward(with_beta = 1) on the same workspace and inputs (an addition to version 13: MRNNT_VERSION and every
+ * struct are unchanged, so callers that may meet an older build of version 13 probe for the symbols mrnnt_sample /
+ * mrnnt_cpu_sample / mrnnt_joint_sample). The third read-out of the lattice next to mrnnt_align (max) and
+ * mrnnt_posteriors (sum). A walker starts at s = 0 before frame 0 and goes forward in time. On row (t, s), with
+ * beta(T, s) = [s == S ? 0 : -inf]:
+ *     x = lpb(t, s) + beta(t+1, s)       the blank arc; -inf when it would leave the monotonic band (T-1-t < S-s)
+ *     y = lpe(t, s) + beta(t+1, s+1)     the label arc; -inf at s = S
+ *     p_label = 1 / (1 + exp(x - y))     fp64; y = -inf: 0, else x = -inf: 1; the two arcs sum to exactly 1
+ *     frame t emits labels[b, s] (and s += 1) iff u(b, k, t) < p_label, else blank (a NaN p_label emits blank)
+ * With a restricting alignment the draws come from the restricted distribution (its band is -inf in the state).
+ * Random numbers (the contract, identical on both devices): Philox4x32-10 with key (seed low 32 bits, seed high 32
+ * bits) and counter (t >> 2, first_sample + k, b, 0x4D524E54); frame t uses output word t & 3 as
+ * u = (word + 0.5) * 2^-32. So sample (b, k) depends on (seed, b, first_sample + k, t) and the state alone -- not on
+ * num_samples, the other utterances or the launch: results are bitwise reproducible, and a call with 8 samples
+ * returns the first 8 of a call with 64.
+ *   alignments_dev[(b*num_samples + k)*out_stride + t], t < T_b: the label frame t emits or p->blank -- the format
+ *       mrnnt_problem.alignment consumes with align_blank == blank; T_b <= t < out_stride: p->blank.
+ *   path_costs_dev[b*num_samples + k] (may be NULL): fp32 of -sum_t lp(chosen arc), summed in fp64 in frame order:
+ *       the negative log-probability of that path under the model.
+ * Sentinels, as mrnnt_align: an utterance whose log-likelihood is not finite has all its num_samples rows -1 and its
+ * path costs +inf (no path) or NaN (a NaN / +inf logit in its band); the other utterances are bit-identical to a call
+ * without it. Device-resident lengths that failed the forward's validation: every row -1 and every path cost NaN.
+ * lengths_on_device and T_b > out_stride: that utterance's rows -1, its path costs NaN, nothing written past the
+ * stride, *status_host raised.
+ * Checked on the host before any device call (RNNT_STATUS_INVALID_VALUE): num_samples >= 1; first_sample >= 0 and
+ * first_sample + num_samples <= 2^32; alignments_dev != NULL; out_stride >= max T_b (host lengths).
+ * Reads the workspace, labels and the lengths (never acts); no new workspace and no size query; no host read,
+ * capturable; asynchronous on `stream`. Its launch counts under [2] of mrnnt_profile_read. */
+RNNTStatus mrnnt_sample(const mrnnt_problem *p, const void *workspace, int num_samples, uint64_t seed,
+                        int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
+                        hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -235,6 +268,13 @@ RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *workspace, size_t works
 RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *workspace, float *blank_post, float *label_post,
                                 float *emit, int64_t emit_stride, float *label_time, int64_t time_stride,
                                 int num_threads);
+
+/* mrnnt_sample for the host implementation, after mrnnt_cpu_forward(with_beta = 1) on the same workspace: host
+ * buffers, the same walk, random numbers, sentinels and checks (the same integer code and decision rule; a sample
+ * can differ from the device's only where some frame's u lies within the two states' rounding of its p_label). */
+RNNTStatus mrnnt_cpu_sample(const mrnnt_problem *p, const void *workspace, int num_samples, uint64_t seed,
+                            int64_t first_sample, int *alignments, int64_t out_stride, float *path_costs,
+                            int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the
@@ -324,6 +364,14 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *p, const void *work
                                   float *label_post_dev, int64_t grid_T, int64_t grid_S1, float *emit_dev,
                                   int64_t emit_stride, float *label_time_dev, int64_t time_stride, hipStream_t stream);
 
+/* mrnnt_sample for the fused joint, after mrnnt_joint_forward(with_beta = 1) on the same workspace and inputs: the
+ * same walk, random numbers, outputs ([B, num_samples, out_stride] / [B, num_samples]), sentinels and host checks
+ * (the joint's lengths are on the host: out_stride >= max T_b is checked here). The same launch on the joint's packed
+ * lattice; reads the workspace, labels and the lengths only. Counts under [2] of mrnnt_profile_read. */
+RNNTStatus mrnnt_joint_sample(const mrnnt_joint_problem *p, const void *workspace, int num_samples, uint64_t seed,
+                              int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
+                              hipStream_t stream);
+
 /* After mrnnt_joint_forward(with_beta=1): list the live lattice rows (those with a non-zero fp32 logit
  * gradient) in the workspace and write their number to *count_dev (device uint64). */
 RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *p, void *workspace, unsigned long long *count_dev,
@@ -376,7 +424,7 @@ int mrnnt_version(void);
  * recorded events and returns per-kernel totals in ms and launch counts for
  *   [0] band, [1] log-softmax row reduce, [2] alpha/beta DP, [3] logit gradient, [4] setup,
  *   [5] joint forward, [6] joint backward, [7] joint reduce, [8] chase launch (log-softmax + alpha/beta),
- *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch and mrnnt_posteriors count under [2]. */
+ *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch, mrnnt_posteriors and mrnnt_sample count under [2]. */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

@@ -222,6 +222,15 @@ RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *ws, float *blank
     return RNNT_STATUS_SUCCESS;
 }
 
+RNNTStatus mrnnt_sample(const mrnnt_problem *p, const void *ws, int num_samples, uint64_t seed, int64_t first_sample,
+                        int *alignments_dev, int64_t out_stride, float *path_costs_dev, hipStream_t stream) {
+    Plan pl;
+    const RNNTStatus st = make_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    return sample_readout(p, pl, ws, num_samples, seed, first_sample, alignments_dev, out_stride, path_costs_dev,
+                          stream);
+}
+
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,
                              hipStream_t stream) {
     Plan pl;

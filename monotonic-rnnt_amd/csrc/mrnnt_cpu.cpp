@@ -31,6 +31,7 @@
 #include "mrnnt.h"
 #pragma GCC visibility pop
 #include "mrnnt_host.h"
+#include "mrnnt_sample.h"
 
 using mrnnt::set_error;
 
@@ -671,6 +672,64 @@ RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *b
         for (int b = 0; b < pl.B; ++b)
             std::fill(label_time + (int64_t)b * time_stride + p->S_host[b], label_time + (int64_t)(b + 1) * time_stride,
                       -1.0f);
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+// mrnnt_sample on the host (the HIP path's mrnnt_sample.hip): the same walk with the random numbers and the decision
+// rule of mrnnt_sample.h, one (utterance, sample) per loop iteration.
+RNNTStatus mrnnt_cpu_sample(const mrnnt_problem *p, const void *ws, int num_samples, uint64_t seed, int64_t first_sample,
+                            int *alignments, int64_t out_stride, float *path_costs, int num_threads) {
+    CpuPlan pl;
+    RNNTStatus st = make_cpu_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (num_samples < 1)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "num_samples must be >= 1, got " + std::to_string(num_samples));
+    if (first_sample < 0 || first_sample + (int64_t)num_samples > ((int64_t)1 << 32))
+        return set_error(RNNT_STATUS_INVALID_VALUE, "sample indices [first_sample, first_sample + num_samples) = [" +
+                                                        std::to_string(first_sample) + ", " +
+                                                        std::to_string(first_sample + (int64_t)num_samples) +
+                                                        ") must lie in [0, 2^32]");
+    if (!alignments) return set_error(RNNT_STATUS_INVALID_VALUE, "alignments is null");
+    if (out_stride < pl.T_max)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(out_stride) +
+                                                        " < max input length " + std::to_string(pl.T_max));
+    if (!ws) return set_error(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
+    const Views w = views(pl, const_cast<void *>(ws));
+    const int nt = threads_of(num_threads);
+    constexpr float nan = std::numeric_limits<float>::quiet_NaN();
+#pragma omp parallel for schedule(dynamic, 8) num_threads(nt)
+    for (int64_t i = 0; i < (int64_t)pl.B * num_samples; ++i) {
+        const int b = (int)(i / num_samples);
+        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+        int *row = alignments + i * out_stride;
+        const double ll = w.ll[b];
+        if (!std::isfinite(ll)) {  // -inf: no path (+inf cost); NaN / +inf: NaN
+            std::fill(row, row + out_stride, -1);
+            if (path_costs) path_costs[i] = ll == kNegInf ? std::numeric_limits<float>::infinity() : nan;
+            continue;
+        }
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const uint32_t smp = (uint32_t)(first_sample + i % num_samples);
+        const double *pb = w.lpb + pl.row_off[b], *pe = w.lpe + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
+        uint32_t word[4] = {0, 0, 0, 0};
+        int s = 0;
+        double cost = 0.0;
+        for (int t = 0; t < T; ++t) {
+            if ((t & 3) == 0) mrnnt::sample_block(seed, (uint32_t)(t >> 2), smp, (uint32_t)b, word);
+            const int64_t r = (int64_t)t * W + s;
+            const bool last = t == T - 1;
+            double x = kNegInf, y = kNegInf;
+            if (T - 1 - t >= S - s) x = pb[r] + (last ? 0.0 : Bt[r + W]);  // else the blank arc leaves the band
+            if (s < S) y = pe[r] + (last ? (s + 1 == S ? 0.0 : kNegInf) : Bt[r + W + 1]);
+            const bool take = mrnnt::sample_uniform(word[t & 3]) < mrnnt::sample_p_label(x, y) && s < S;
+            cost += take ? pe[r] : pb[r];
+            row[t] = take ? lab[s] : p->blank;
+            s += take ? 1 : 0;
+        }
+        std::fill(row + T, row + out_stride, p->blank);
+        if (path_costs) path_costs[i] = (float)(-cost);
     }
     return RNNT_STATUS_SUCCESS;
 }

@@ -274,6 +274,19 @@ struct PosteriorArgs {
 // one launch; col_blocks: its column workgroups (16 waves, one lattice column per wave, grid-stride)
 hipError_t launch_posteriors(const DevProblem &p, const PosteriorArgs &a, int col_blocks, hipStream_t stream);
 
+// mrnnt_sample (mrnnt_sample.hip): alignments drawn from the path posterior, read out of the workspace of a forward
+// with beta. out: [B, num_samples, out_stride] alignment rows; costs: [B, num_samples] or null.
+struct SampleArgs {
+    int *out;
+    int64_t out_stride;
+    float *costs;
+    int num_samples;
+    int64_t first_sample;  // sample index of k = 0 (first_sample + num_samples <= 2^32)
+    uint64_t seed;
+};
+// one launch, one wave per (utterance, 64 samples)
+hipError_t launch_sample(const DevProblem &p, const SampleArgs &a, hipStream_t stream);
+
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that
 // published it (never cleared: every launch derives a tag of its own from its dispatch id).

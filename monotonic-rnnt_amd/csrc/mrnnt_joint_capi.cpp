@@ -1,7 +1,7 @@
 // mrnnt_joint_capi.cpp -- the fused joint network + loss ABI of libmonotonic_rnnt_amd.so (mrnnt_joint_* in
 // include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint.hip,
-// mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors put the Viterbi launch / the posterior read-out of
-// the loss ABI behind the joint's log-softmax pass. Asynchronous on the caller's stream, no host synchronisation.
+// mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors / mrnnt_joint_sample put the Viterbi launch / the
+// posterior read-out / the path sampler of the loss ABI behind the joint's log-softmax pass. Asynchronous on the caller's stream, no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -238,6 +238,18 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws,
     const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
     if (e != hipSuccess) return fail_hip(e, "posterior kernel");
     return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_sample(const mrnnt_joint_problem *jp, const void *ws, int num_samples, uint64_t seed,
+                              int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
+                              hipStream_t stream) {
+    JointPlan jl;
+    const RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    // the joint plans its lattice packed and the outputs are [B, K, out_stride]: mrnnt_sample's launch as it is
+    const mrnnt_problem p = base_problem(jp);
+    return sample_readout(&p, jl.base, ws, num_samples, seed, first_sample, alignments_dev, out_stride, path_costs_dev,
+                          stream);
 }
 
 RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *jp, void *ws, unsigned long long *count_dev,

@@ -362,6 +362,33 @@ RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProb
     return RNNT_STATUS_SUCCESS;
 }
 
+RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws, int num_samples, uint64_t seed,
+                          int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
+                          hipStream_t stream) {
+    if (num_samples < 1)
+        return fail(RNNT_STATUS_INVALID_VALUE, "num_samples must be >= 1, got " + std::to_string(num_samples));
+    if (first_sample < 0 || first_sample + (int64_t)num_samples > ((int64_t)1 << 32))
+        return fail(RNNT_STATUS_INVALID_VALUE, "sample indices [first_sample, first_sample + num_samples) = [" +
+                                                   std::to_string(first_sample) + ", " +
+                                                   std::to_string(first_sample + (int64_t)num_samples) +
+                                                   ") must lie in [0, 2^32]");
+    if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
+    // with device lengths the kernel bounds every write by the stride instead (and raises the status word)
+    if (out_stride < 1 || (!pl.dyn && out_stride < pl.T_max))
+        return fail(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(out_stride) +
+                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
+    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (!p->T_dev || !p->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
+    if (!p->labels) return fail(RNNT_STATUS_INVALID_VALUE, "labels is null");
+    DevProblem d = make_dev(p, pl, ws);  // acts are never read
+    RNNTStatus st;
+    if (pl.dyn && (st = status_device_ptr(p, &d.status_host)) != RNNT_STATUS_SUCCESS) return st;
+    const SampleArgs a{alignments_dev, out_stride, path_costs_dev, num_samples, first_sample, seed};
+    const hipError_t e = timed(K_DP, stream, [&] { return launch_sample(d, a, stream); });
+    if (e != hipSuccess) return fail_hip(e, "sample kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
 // ---- profiling ---------------------------------------------------------------------------------
 
 static std::mutex g_prof_mu;

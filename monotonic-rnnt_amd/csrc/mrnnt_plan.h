@@ -84,6 +84,12 @@ struct LatticeOpts {
 RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProblem &d, void *ws,
                            const LatticeOpts &o, hipStream_t stream);
 
+// mrnnt_sample / mrnnt_joint_sample after their plans: the host checks (before any device call), then the sampler
+// launch on the plan's lattice (counted under K_DP).
+RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws, int num_samples, uint64_t seed,
+                          int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
+                          hipStream_t stream);
+
 // ---- profiling (mrnnt_profile_enable / mrnnt_profile_read) ------------------------------------------------------
 struct ProfRec {
     int id;

@@ -153,10 +153,13 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_cpu_align": (i, [P, vp, sz, vp, i64, vp, i]),
         "mrnnt_posteriors": (i, [P, vp, vp, vp, vp, i64, vp, i64, vp]),
         "mrnnt_cpu_posteriors": (i, [P, vp, vp, vp, vp, i64, vp, i64, i]),
+        "mrnnt_sample": (i, [P, vp, i, ctypes.c_uint64, i64, vp, i64, vp, vp]),
+        "mrnnt_cpu_sample": (i, [P, vp, i, ctypes.c_uint64, i64, vp, i64, vp, i]),
         "mrnnt_joint_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_forward": (i, [JP, vp, sz, vp, i, vp]),
         "mrnnt_joint_align": (i, [JP, vp, sz, vp, i64, vp, vp]),
         "mrnnt_joint_posteriors": (i, [JP, vp, vp, vp, i64, i64, vp, i64, vp, i64, vp]),
+        "mrnnt_joint_sample": (i, [JP, vp, i, ctypes.c_uint64, i64, vp, i64, vp, vp]),
         "mrnnt_joint_live_rows": (i, [JP, vp, vp, vp]),
         "mrnnt_joint_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp, vp]),
         "mrnnt_joint_reduce": (i, [JP, vp, i64, vp, vp, vp, vp, vp]),

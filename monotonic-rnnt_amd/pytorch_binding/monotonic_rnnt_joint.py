@@ -38,10 +38,10 @@ import torch
 
 try:
     from . import _mrnnt_lib as _L
-    from .monotonic_rnnt_op import Posteriors, _check_labels, _lengths
+    from .monotonic_rnnt_op import Posteriors, Samples, _check_labels, _lengths, _sample_args
 except ImportError:
     import _mrnnt_lib as _L
-    from monotonic_rnnt_op import Posteriors, _check_labels, _lengths
+    from monotonic_rnnt_op import Posteriors, Samples, _check_labels, _lengths, _sample_args
 
 _L.load()
 
@@ -146,6 +146,16 @@ class _JointPrepared:
                                                       Sg, _vp(emit), Tg, _vp(label_time), label_width,
                                                       self.stream()), "mrnnt_joint_posteriors")
         return Posteriors(blank, label, emit, label_time, costs)
+
+    def sample(self, K: int, seed: int, first: int, L: int) -> Samples:
+        """The forward with beta, then mrnnt_joint_sample on its workspace."""
+        costs, ws = self.forward(with_beta=True)
+        with torch.cuda.device(self.device):
+            out = torch.empty((self.B, K, L), dtype=torch.int32, device=self.device)
+            path_costs = torch.empty((self.B, K), dtype=torch.float32, device=self.device)
+            _L.check(_L.load().mrnnt_joint_sample(ctypes.byref(self.problem), _vp(ws), K, seed, first, _vp(out), L,
+                                                  _vp(path_costs), self.stream()), "mrnnt_joint_sample")
+        return Samples(out, path_costs, costs)
 
     def backward_rows(self, ws, grad_scale, with_index=False, bias_column=False, dbias=None, capturable=False):
         """The fused gradient pass over the live rows: (G [n, V], Hact [n, H]) and, with_index, the enc / pred
@@ -401,5 +411,29 @@ def monotonic_rnnt_joint_posteriors(enc: torch.Tensor, pred: torch.Tensor, weigh
     return prep.posteriors(labels.size(1) if labels.dim() == 2 else prep.labels.size(1))
 
 
+def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                                bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
+                                label_lengths: torch.Tensor, num_samples: int, seed: int, first_sample: int = 0,
+                                blank_label: int = 0, alignment: Optional[torch.Tensor] = None,
+                                max_distance_from_alignment: int = 0,
+                                max_input_length: Optional[int] = None) -> Samples:
+    """Alignments drawn from the path posterior under the joint network, without materialising its logits: the fused
+    forward with beta, then mrnnt_joint_sample on its workspace. Arguments as monotonic_rnnt_joint_loss plus
+    num_samples / seed / first_sample as monotonic_rnnt_sample, whose random numbers and decision rule it shares.
+
+    Returns monotonic_rnnt_sample's namedtuple (alignments int32 [B, num_samples, L], path_costs float32
+    [B, num_samples], costs float32 [B]); L is max T_b, or max_input_length (>= every T_b) when given. An utterance
+    without a finite cost has its rows -1 and path costs +inf / NaN. Not differentiable: plain tensors are returned."""
+    K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_joint_sample")
+    prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
+                          blank_label, alignment, max_distance_from_alignment)
+    L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
+    if L < 1:
+        raise RuntimeError(f"monotonic_rnnt_joint_sample: max_input_length must be >= 1, got {L}")
+    if K < 1:
+        raise RuntimeError(f"monotonic_rnnt_joint_sample: num_samples must be >= 1, got {K}")
+    return prep.sample(K, seed, first, L)
+
+
 __all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_joint_align",
-           "monotonic_rnnt_joint_posteriors"]
+           "monotonic_rnnt_joint_posteriors", "monotonic_rnnt_joint_sample"]

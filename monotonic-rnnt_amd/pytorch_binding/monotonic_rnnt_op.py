@@ -531,6 +531,76 @@ def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_le
     return Posteriors(blank, label, emit, label_time, costs)
 
 
+Samples = collections.namedtuple("Samples", ["alignments", "path_costs", "costs"])
+
+
+def _sample_args(num_samples, seed, first_sample, where):
+    """(num_samples, seed as uint64, first_sample) as the library takes them; the library checks the ranges."""
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 64):
+        raise RuntimeError(f"{where}: seed must fit in 64 bits, got {seed}")
+    return int(num_samples), seed & ((1 << 64) - 1), int(first_sample)
+
+
+def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                          label_lengths: torch.Tensor, num_samples: int, seed: int, first_sample: int = 0,
+                          alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
+                          blank_label: int = 0, max_input_length: Optional[int] = None) -> Samples:
+    """Whole alignments drawn from the path posterior p(path | labels, acts) of the lattice the loss sums over
+    (mrnnt_sample / mrnnt_cpu_sample, include/mrnnt.h): the forward pass with beta, then a read-out of its workspace
+    on the same stream. Arguments as monotonic_rnnt_loss; with `alignment` and `max_distance_from_alignment` the
+    draws come from the restricted distribution (k = 0 returns the given alignment).
+
+    Returns the namedtuple (alignments, path_costs, costs) on acts.device:
+        alignments: int32 [B, num_samples, L]. Row (b, k) holds, for t < T_b, the label frame t emits or blank_label
+                    -- the format `alignment=` of the loss consumes -- and blank_label for t >= T_b. L is chosen as
+                    monotonic_rnnt_posteriors chooses it: max T_b for host lengths, acts.size(1) for padded 4-D acts,
+                    else max_input_length (>= every T_b) or alignment.size(1).
+        path_costs: float32 [B, num_samples], the negative log-probability of each drawn path under the model
+                    (>= costs; exp(costs - path_costs) is the probability of drawing it).
+        costs:      float32 [B], the loss of the same inputs.
+    Random numbers are counter-based (Philox4x32-10 keyed by `seed`, counted by frame, sample index first_sample + k
+    and utterance index): the same call gives the same bits, num_samples = 8 gives the first 8 rows of num_samples =
+    64, and first_sample = 8 continues where 8 samples stopped. An utterance without a finite cost has all its rows
+    -1 and path costs +inf (no path) or NaN; the others are unaffected. Not differentiable: requires_grad is ignored
+    and plain tensors are returned. GPU-resident lengths that fail validation give -1 / NaN everywhere and surface
+    through check_lengths() exactly as for the loss."""
+    K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_sample")
+    acts = acts.detach()
+    prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
+    if max_input_length is not None:
+        L = int(max_input_length)
+    elif prep.acts.dim() == 4:
+        L = prep.acts.size(1)
+    elif not prep.dyn:
+        L = int(prep.T_host.max())
+    elif prep.alignment is not None:
+        L = prep.alignment.size(1)
+    else:
+        raise RuntimeError("monotonic_rnnt_sample: with GPU-resident lengths and packed acts the longest input "
+                           "length is not known on the host; pass max_input_length (>= every input length)")
+    if L < 1:
+        raise RuntimeError(f"monotonic_rnnt_sample: max_input_length must be >= 1, got {L}")
+    if K < 1:
+        raise RuntimeError(f"monotonic_rnnt_sample: num_samples must be >= 1, got {K}")
+    costs, ws = _forward(prep, with_beta=True)
+    B, dev = prep.problem.B, prep.device
+    out = torch.empty((B, K, L), dtype=torch.int32, device=dev)
+    path_costs = torch.empty((B, K), dtype=torch.float32, device=dev)
+    lib = _L.load()
+    if not prep.on_gpu:
+        _L.check(lib.mrnnt_cpu_sample(ctypes.byref(prep.problem), _ptr(ws), K, seed, first, _ptr(out), L,
+                                      _ptr(path_costs), prep.num_threads), "mrnnt_cpu_sample")
+        return Samples(out, path_costs, costs)
+    with _on_device(dev):
+        _L.check(lib.mrnnt_sample(ctypes.byref(prep.problem), _ptr(ws), K, seed, first, _ptr(out), L,
+                                  _ptr(path_costs), prep.stream()), "mrnnt_sample")
+        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.current_stream(dev).synchronize()
+            check_lengths(sync=False)
+    return Samples(out, path_costs, costs)
+
+
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
@@ -601,4 +671,4 @@ class _Ext:
 monotonic_rnnt_cpp = _Ext()
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
-           "monotonic_rnnt_align", "monotonic_rnnt_posteriors"]
+           "monotonic_rnnt_align", "monotonic_rnnt_posteriors", "monotonic_rnnt_sample"]
