@@ -200,6 +200,47 @@ RNNTStatus mrnnt_sample(const mrnnt_problem *p, const void *workspace, int num_s
                         int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
                         hipStream_t stream);
 
+/* Differentiable scores of GIVEN alignments (an addition to version 13: MRNNT_VERSION and every struct are unchanged,
+ * so callers that may meet an older build of version 13 probe for the symbols mrnnt_path_forward / mrnnt_cpu_path_forward).
+ * The read-outs above take paths out of the lattice (mrnnt_align the best one, mrnnt_sample draws); this pair scores
+ * num_paths of them per utterance and returns the logit gradient of sum_{b,k} w[b, k] * path_costs[b, k] -- Viterbi
+ * training, risk-weighted / MWER / REINFORCE objectives over sampled paths (signed weights), latency penalties -- in one
+ * forward and ONE dense gradient pass whatever num_paths is.
+ *   alignments_dev[(b*num_paths + k)*path_stride + t], t < T_b: p->blank, or the label frame t emits -- the format
+ *       mrnnt_align / mrnnt_sample write. Entries at t >= T_b are not read.
+ * Walk of row (b, k), from s = 0: at frame t an entry equal to p->blank takes the blank arc of row (t, s); an entry
+ * equal to labels[b, s] with s < S_b takes the label arc, then s += 1; anything else (a wrong label, a negative value,
+ * the -1 sentinel rows, a label at s = S_b) makes the row INVALID, and so does s != S_b after frame T_b - 1.
+ * Forward: path_costs_dev[b*num_paths + k] (may be NULL) = fp32(-sum_t lp(arc_t)), lp = z[row, v] + den[row] as the
+ *   loss forms it, summed in fp64 in a fixed order (bitwise reproducible). An invalid row costs +inf. A path through a
+ *   -inf logit costs +inf; a NaN or +inf logit in a visited row gives NaN for the paths that visit it; the other paths
+ *   and utterances are bit-identical to a call without it. The log-softmax reads only the rows between the lowest and
+ *   the highest valid path of each frame (the hull), plus row (0, 0) of an utterance without a valid path.
+ * Backward (after mrnnt_path_forward on the same workspace, problem and alignments): weights_dev[b*num_paths + k]
+ *   (fp32, signed; NULL = 1) is the upstream gradient of path_costs. With Wb(r) / We(r) the sums of w[b, k] over the
+ *   VALID paths that take the blank / label arc out of row r, accumulated in fp64 in ascending k, and Wocc = Wb + We,
+ *       grads[r, v] = Wocc(r) softmax(z_r)[v] - [v == blank] Wb(r) - [v == label(s)] We(r).
+ *   The weight of an invalid path is ignored. A row with Wb == 0 && We == 0 (unvisited, outside every path, an
+ *   utterance without a valid path, all-zero weights) is stored as exact zeros and its acts are not read (a NaN logit
+ *   there gives 0); Wb = -We != 0 is a live row with Wocc = 0. Padding rows of the padded layout are 0. grads has the
+ *   layout and element type of acts; no pre-zeroing; every gradient is bitwise reproducible.
+ * Takes everything mrnnt_forward's log-softmax pass takes (bf16 / fp16 acts, the padded layout, device-resident
+ * lengths: no host read, capturable; T_b <= path_stride then joins the device validation, and a failed validation
+ * makes every path cost and gradient NaN and raises *status_host, as the loss does) except a restricting alignment:
+ * the band arrays of the workspace hold the hull.
+ * Checked on the host before any device call, workspace included (RNNT_STATUS_INVALID_VALUE): p->alignment == NULL;
+ * num_paths >= 1; alignments_dev != NULL; path_stride >= max T_b (host lengths).
+ * Workspace: mrnnt_path_workspace_size(p, num_paths) bytes (>= mrnnt_workspace_size: the loss's arrays, the band
+ * arrays and a few words per path); Wb / We use its alpha / beta arrays. Asynchronous on `stream`. The new launches
+ * count under [2] of mrnnt_profile_read, the log-softmax under [1], the gradient under [3]. */
+RNNTStatus mrnnt_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes);
+RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                              const int *alignments_dev, int num_paths, int64_t path_stride, float *path_costs_dev,
+                              hipStream_t stream);
+RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                               const int *alignments_dev, int num_paths, int64_t path_stride, const float *weights_dev,
+                               void *grads, hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -275,6 +316,16 @@ RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *workspace, f
 RNNTStatus mrnnt_cpu_sample(const mrnnt_problem *p, const void *workspace, int num_samples, uint64_t seed,
                             int64_t first_sample, int *alignments, int64_t out_stride, float *path_costs,
                             int num_threads);
+
+/* mrnnt_path_workspace_size / mrnnt_path_forward / mrnnt_path_backward for the host implementation: host buffers
+ * (fp32 acts), the same walk, validity rule, sums (fp64, frame order / ascending k), exact zeros and host checks.
+ * grads may be acts itself (in place), as in mrnnt_cpu_backward. */
+RNNTStatus mrnnt_cpu_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes);
+RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, const int *alignments,
+                                  int num_paths, int64_t path_stride, float *path_costs, int num_threads);
+RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, const int *alignments,
+                                   int num_paths, int64_t path_stride, const float *weights, float *grads,
+                                   int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the
@@ -424,7 +475,9 @@ int mrnnt_version(void);
  * recorded events and returns per-kernel totals in ms and launch counts for
  *   [0] band, [1] log-softmax row reduce, [2] alpha/beta DP, [3] logit gradient, [4] setup,
  *   [5] joint forward, [6] joint backward, [7] joint reduce, [8] chase launch (log-softmax + alpha/beta),
- *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch, mrnnt_posteriors and mrnnt_sample count under [2]. */
+ *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch, mrnnt_posteriors and mrnnt_sample count under [2],
+ *   and so do the walk, score and coefficient launches of mrnnt_path_forward / mrnnt_path_backward (their log-softmax
+ *   under [1], their gradient under [3]). */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

@@ -231,6 +231,136 @@ RNNTStatus mrnnt_sample(const mrnnt_problem *p, const void *ws, int num_samples,
                           stream);
 }
 
+}  // extern "C"
+
+namespace {
+
+// mrnnt_path_*: the loss's plan with band arrays (the hull of the paths), then the per-path words.
+struct PathPlan {
+    Plan pl;
+    size_t off_valid = 0, off_carry = 0, total = 0;
+};
+
+// The plan and the host checks of the path entry points, all before any device call.
+RNNTStatus make_path_plan(const mrnnt_problem *p, int num_paths, PathPlan *pp) {
+    if (p && p->alignment)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL: "
+                                               "the band arrays hold the hull of the given paths)");
+    if (num_paths < 1)
+        return fail(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
+    const RNNTStatus st = make_plan(p, &pp->pl, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = pp->pl;
+    if ((int64_t)pl.B * num_paths > 0x7fffffff || pl.B > 65535)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take B <= 65535 and B * num_paths < 2^31");
+    size_t o = pl.total;
+    pp->off_valid = o;
+    o = align_up(o + sizeof(int) * (size_t)pl.B * num_paths);
+    pp->off_carry = o;
+    o = align_up(o + sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
+    pp->total = o;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride) {
+    if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
+    // with device lengths T_b <= path_stride joins the device validation
+    if (path_stride < 1 || (!pl.dyn && path_stride < pl.T_max))
+        return fail(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(path_stride) +
+                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
+    return RNNT_STATUS_SUCCESS;
+}
+
+PathArgs path_args(const PathPlan &pp, void *ws, const int *alignments_dev, int num_paths, int64_t path_stride) {
+    PathArgs a;
+    a.al = alignments_dev;
+    a.stride = path_stride;
+    a.K = num_paths;
+    a.valid = carve<int>(ws, pp.off_valid);
+    a.carry = carve<int>(ws, pp.off_carry);
+    a.min_s = carve<int>(ws, pp.pl.off_min);
+    a.max_s = carve<int>(ws, pp.pl.off_max);
+    a.costs = nullptr;
+    a.w = nullptr;
+    return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    PathPlan pp;
+    const RNNTStatus st = make_path_plan(p, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = pp.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                              int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream) {
+    PathPlan pp;
+    RNNTStatus st = make_path_plan(p, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = pp.pl;
+    if ((st = check_paths(pl, alignments_dev, path_stride)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, pl, ws);  // d.min_s / d.max_s: the hull
+    LatticeOpts o;
+    o.t_cap = path_stride;
+    if ((tuning().col_scatter & 3) != 0 && !(tuning().col_xcd & 3))  // the gradient's column order, as mrnnt_forward
+        o.scatter_above = (int64_t)streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    if ((st = prepare_lattice(p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
+    PathArgs a = path_args(pp, ws, alignments_dev, num_paths, path_stride);
+    a.costs = path_costs_dev;
+    hipError_t e = timed(K_DP, stream, [&] { return launch_path_walk(d, a, pl.T_max, stream); });
+    if (e != hipSuccess) return fail_hip(e, "path walk kernels");
+    // the log-softmax over the hull rows: the launch of mrnnt_align, its alignment window the hull
+    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
+    DevProblem ds = d;
+    ds.col_mul = column_order(pl, 1);
+    if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {
+        grid = streaming_grid(pl.cols, kStealGridPerCU);
+        ds.steal = grid < pl.cols;
+    }
+    e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
+    if (path_costs_dev) {
+        e = timed(K_DP, stream, [&] { return launch_path_score(d, a, stream); });
+        if (e != hipSuccess) return fail_hip(e, "path score kernel");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                               int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                               hipStream_t stream) {
+    PathPlan pp;
+    RNNTStatus st = make_path_plan(p, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = pp.pl;
+    if ((st = check_paths(pl, alignments_dev, path_stride)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, pl, ws);
+    PathArgs a = path_args(pp, ws, alignments_dev, num_paths, path_stride);
+    a.w = weights_dev;
+    hipError_t e = timed(K_DP, stream, [&] { return launch_path_coef(d, a, pl.T_max, stream); });
+    if (e != hipSuccess) return fail_hip(e, "path coefficient kernel");
+    d.col_mul = column_order(pl, 2);
+    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    e = timed(K_GRAD, stream, [&] { return launch_path_grad(d, pl.elem, grads, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "path gradient kernel");
+    if (pl.pad_S1 != 0) {
+        e = launch_pad_zero(d, pl.elem, grads, stream);
+        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,
                              hipStream_t stream) {
     Plan pl;

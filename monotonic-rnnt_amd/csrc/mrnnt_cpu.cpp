@@ -135,7 +135,8 @@ struct CpuPlan {
 constexpr size_t kAlign = 64;
 size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
-RNNTStatus make_cpu_plan(const mrnnt_problem *p, CpuPlan *pl) {
+// band: the plan holds the band arrays although the problem has no alignment (mrnnt_cpu_path_*: the paths' hull)
+RNNTStatus make_cpu_plan(const mrnnt_problem *p, CpuPlan *pl, bool band = false) {
     if (!p) return set_error(RNNT_STATUS_INVALID_VALUE, "null problem");
     if (p->B <= 0) return set_error(RNNT_STATUS_INVALID_VALUE, "B must be > 0");
     if (p->V <= 0) return set_error(RNNT_STATUS_INVALID_VALUE, "V must be > 0");
@@ -165,8 +166,8 @@ RNNTStatus make_cpu_plan(const mrnnt_problem *p, CpuPlan *pl) {
     if (q.S_max > 0 && p->label_stride < q.S_max)
         return set_error(RNNT_STATUS_INVALID_VALUE, "label row stride " + std::to_string(p->label_stride) +
                                                         " < max label length " + std::to_string(q.S_max));
-    q.align = p->alignment != nullptr;
-    if (q.align && p->align_stride < q.T_max)
+    q.align = p->alignment != nullptr || band;
+    if (p->alignment && p->align_stride < q.T_max)
         return set_error(RNNT_STATUS_INVALID_VALUE, "alignment row stride " + std::to_string(p->align_stride) +
                                                         " < max input length " + std::to_string(q.T_max));
     q.pad_T = p->pad_T;
@@ -730,6 +731,193 @@ RNNTStatus mrnnt_cpu_sample(const mrnnt_problem *p, const void *ws, int num_samp
         }
         std::fill(row + T, row + out_stride, p->blank);
         if (path_costs) path_costs[i] = (float)(-cost);
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+}  // extern "C"
+
+// ---- mrnnt_cpu_path_*: scores of given alignments and their logit gradient (the HIP path's mrnnt_path.hip) ----------
+namespace {
+
+constexpr int kHullEmpty = 1 << 29;
+
+struct CpuPathPlan {
+    CpuPlan pl;
+    size_t off_valid = 0, total = 0;
+};
+
+// the plan (with band arrays: the hull) and the host checks, in the order of the HIP path's
+RNNTStatus make_cpu_path_plan(const mrnnt_problem *p, int num_paths, const int *alignments, int64_t path_stride,
+                              bool sizing, CpuPathPlan *pp) {
+    if (p && p->alignment)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be "
+                                                    "NULL: the band arrays hold the hull of the given paths)");
+    if (num_paths < 1)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
+    const RNNTStatus st = make_cpu_plan(p, &pp->pl, true);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    pp->off_valid = pp->pl.total;
+    pp->total = align_up(pp->off_valid + sizeof(int) * (size_t)pp->pl.B * num_paths);
+    if (sizing) return RNNT_STATUS_SUCCESS;
+    if (!alignments) return set_error(RNNT_STATUS_INVALID_VALUE, "alignments is null");
+    if (path_stride < pp->pl.T_max)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(path_stride) +
+                                                        " < max input length " + std::to_string(pp->pl.T_max));
+    return RNNT_STATUS_SUCCESS;
+}
+
+// The walk of one alignment row: calls visit(t, s, label_arc) for every frame while the row is valid; returns
+// validity (every entry blank or labels[b, s] with s < S, and s == S at the end).
+template <class F>
+inline bool walk_path(const int *row, const int *lab, int T, int S, int blank, F &&visit) {
+    int s = 0;
+    for (int t = 0; t < T; ++t) {
+        const int v = row[t];
+        if (v == blank) {
+            visit(t, s, false);
+        } else if (v >= 0 && s < S && v == lab[s]) {
+            visit(t, s, true);
+            ++s;
+        } else {
+            return false;
+        }
+    }
+    return s == S;
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_cpu_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
+    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    CpuPathPlan pp;
+    const RNNTStatus st = make_cpu_path_plan(p, num_paths, nullptr, 0, true, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = pp.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                  int num_paths, int64_t path_stride, float *path_costs, int num_threads) {
+    CpuPathPlan pp;
+    RNNTStatus st = make_cpu_path_plan(p, num_paths, alignments, path_stride, false, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const CpuPlan &pl = pp.pl;
+    if ((st = check_inputs(p, pl)) != RNNT_STATUS_SUCCESS) return st;
+    if (!ws || ws_bytes < pp.total)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pp.total) + " bytes");
+    const Views w = views(pl, ws);
+    int *valid = reinterpret_cast<int *>(static_cast<char *>(ws) + pp.off_valid);
+    const int nt = threads_of(num_threads);
+    const int K = num_paths;
+    // validity, and the hull of the valid paths in the band arrays: min_s = lowest visited row + 1, max_s = highest --
+    // the form whose alignment window (row_window) is exactly [lowest, highest]; no valid path: no rows
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int b = 0; b < pl.B; ++b) {
+        const int T = p->T_host[b], S = p->S_host[b];
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        int *lo = w.min_s + pl.col_off[b], *hi = w.max_s + pl.col_off[b];
+        std::fill(lo, lo + T, kHullEmpty - 1);
+        std::fill(hi, hi + T, -1);
+        for (int k = 0; k < K; ++k) {
+            const int *row = alignments + ((int64_t)b * K + k) * path_stride;
+            const bool ok = walk_path(row, lab, T, S, p->blank, [](int, int, bool) {});
+            valid[(int64_t)b * K + k] = ok ? 1 : 0;
+            if (ok)
+                walk_path(row, lab, T, S, p->blank, [&](int t, int s, bool) {
+                    lo[t] = std::min(lo[t], s);
+                    hi[t] = std::max(hi[t], s);
+                });
+        }
+        for (int t = 0; t < T; ++t) lo[t] += 1;
+    }
+    softmax_pass(p, pl, w, nt);
+    if (!path_costs) return RNNT_STATUS_SUCCESS;
+#pragma omp parallel for schedule(dynamic, 8) num_threads(nt)
+    for (int64_t i = 0; i < (int64_t)pl.B * K; ++i) {
+        const int b = (int)(i / K);
+        if (!valid[i]) {
+            path_costs[i] = std::numeric_limits<float>::infinity();
+            continue;
+        }
+        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const double *pb = w.lpb + pl.row_off[b], *pe = w.lpe + pl.row_off[b];
+        double sum = 0.0;
+        walk_path(alignments + i * path_stride, lab, T, S, p->blank, [&](int t, int s, bool label) {
+            const int64_t r = (int64_t)t * W + s;
+            sum += label ? pe[r] : pb[r];
+        });
+        path_costs[i] = (float)(-sum);
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                   int num_paths, int64_t path_stride, const float *weights, float *grads,
+                                   int num_threads) {
+    CpuPathPlan pp;
+    RNNTStatus st = make_cpu_path_plan(p, num_paths, alignments, path_stride, false, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const CpuPlan &pl = pp.pl;
+    if (!p->acts) return set_error(RNNT_STATUS_INVALID_VALUE, "acts is null");
+    if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
+    if (!grads) return set_error(RNNT_STATUS_INVALID_VALUE, "grads is null");
+    if (!ws || ws_bytes < pp.total)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pp.total) + " bytes");
+    const Views w = views(pl, ws);
+    const int *valid = reinterpret_cast<const int *>(static_cast<const char *>(ws) + pp.off_valid);
+    const int nt = threads_of(num_threads);
+    const int K = num_paths, V = pl.V;
+    // Wb (w.alpha) / We (w.beta): zero over the hull rows, then the valid paths' weights in ascending k
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int b = 0; b < pl.B; ++b) {
+        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lo = w.min_s + pl.col_off[b], *hi = w.max_s + pl.col_off[b];
+        double *wb = w.alpha + pl.row_off[b], *we = w.beta + pl.row_off[b];
+        for (int t = 0; t < T; ++t)
+            for (int s = std::max(lo[t] - 1, 0); s <= std::min(hi[t], S); ++s) wb[(int64_t)t * W + s] = we[(int64_t)t * W + s] = 0.0;
+        for (int k = 0; k < K; ++k) {
+            if (!valid[(int64_t)b * K + k]) continue;
+            const double wk = weights ? (double)weights[(int64_t)b * K + k] : 1.0;
+            walk_path(alignments + ((int64_t)b * K + k) * path_stride, lab, T, S, p->blank, [&](int t, int s, bool label) {
+                if (s < lo[t] - 1 || s > hi[t]) return;  // (a workspace that is not this call's forward's: stay in the hull)
+                (label ? we : wb)[(int64_t)t * W + s] += wk;
+            });
+        }
+    }
+    const float *acts = static_cast<const float *>(p->acts);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
+    for (int64_t c = 0; c < pl.cols; ++c) {
+        const int b = col_utt(pl, c);
+        const int t = (int)(c - pl.col_off[b]);
+        const int S = p->S_host[b], W = S + 1;
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
+        const int lo = w.min_s[c] - 1, hi = std::min(w.max_s[c], S);
+        for (int s = 0; s < W; ++s) {
+            float *g = grads + (a0 + s) * V;
+            const double wb = (s >= lo && s <= hi) ? w.alpha[r0 + s] : 0.0, we = (s >= lo && s <= hi) ? w.beta[r0 + s] : 0.0;
+            if (!(wb != 0.0 || we != 0.0)) {  // exact zeros, acts not read
+                std::fill(g, g + V, 0.0f);
+                continue;
+            }
+            grad_row(acts + (a0 + s) * V, g, V, w.den[r0 + s], (float)(wb + we));
+            g[p->blank] -= (float)wb;
+            if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)we;
+        }
+    }
+    if (pl.pad_S1) {  // padding rows of the padded layout: 0
+#pragma omp parallel for schedule(static) num_threads(nt)
+        for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
+            const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
+            const int s0 = t < p->T_host[b] ? p->S_host[b] + 1 : 0;
+            float *g = grads + (pc * pl.pad_S1 + s0) * V;
+            std::fill(g, g + (pl.pad_S1 - s0) * V, 0.0f);
+        }
     }
     return RNNT_STATUS_SUCCESS;
 }

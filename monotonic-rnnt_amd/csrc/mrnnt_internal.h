@@ -287,6 +287,27 @@ struct SampleArgs {
 // one launch, one wave per (utterance, 64 samples)
 hipError_t launch_sample(const DevProblem &p, const SampleArgs &a, hipStream_t stream);
 
+// mrnnt_path_forward / mrnnt_path_backward (mrnnt_path.hip): scores of K given alignment rows per utterance and
+// their logit gradient. The problem's band arrays (p.min_s / p.max_s) hold the hull of the valid paths, p.alpha /
+// p.beta the per-row weights Wb / We of the blank / label arcs.
+struct PathArgs {
+    const int *al;       // [B, K, stride] alignment rows
+    int64_t stride;
+    int K;
+    int *valid;          // [B, K] 1: the row walks the lattice from (0, 0) to (T_b, S_b)
+    int *carry;          // [path_carry_slots, K] label position of path k before the first frame of a 64-frame block
+    int *min_s, *max_s;  // the band arrays of the plan (written by the hull kernel)
+    float *costs;        // [B, K] or nullptr (score)
+    const float *w;      // [B, K] upstream weights or nullptr = 1 (coef)
+};
+// slots of PathArgs::carry: every utterance's 64-frame blocks in a row, each utterance on a slot of its own
+inline int64_t path_carry_slots(int64_t cols, int B) { return (cols >> 6) + B + 1; }
+// T_bound: a host bound on max T_b (sizes the grid only). walk: validity and carries, then the hull.
+hipError_t launch_path_walk(const DevProblem &p, const PathArgs &a, int T_bound, hipStream_t stream);
+hipError_t launch_path_score(const DevProblem &p, const PathArgs &a, hipStream_t stream);
+hipError_t launch_path_coef(const DevProblem &p, const PathArgs &a, int T_bound, hipStream_t stream);
+hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
+
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that
 // published it (never cleared: every launch derives a tag of its own from its dispatch id).

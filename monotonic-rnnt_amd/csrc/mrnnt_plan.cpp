@@ -122,7 +122,7 @@ static RNNTStatus plan_device_lengths(const mrnnt_problem *p, Plan &q) {
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl) {
+RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl, bool band) {
     if (!p) return fail(RNNT_STATUS_INVALID_VALUE, "null problem");
     if (p->B <= 0) return fail(RNNT_STATUS_INVALID_VALUE, "B must be > 0");
     if (p->V <= 0) return fail(RNNT_STATUS_INVALID_VALUE, "V must be > 0");
@@ -181,7 +181,7 @@ RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl) {
         return fail(RNNT_STATUS_INVALID_VALUE, "acts has " + std::to_string(p->num_rows) + " rows but the " +
                                                    (q.pad_S1 ? "padded layout needs " : "lattice needs sum_b T_b(S_b+1) = ") +
                                                    std::to_string(acts_rows));
-    q.align = p->alignment != nullptr;
+    q.align = p->alignment != nullptr || band;
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
@@ -351,7 +351,7 @@ RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProb
                 [&] { return launch_setup(p->T_dev, p->S_dev, pl.B, row_off, col_off, col_b, nullptr, 0, stream); });
         if (e != hipSuccess) return fail_hip(e, "setup kernel");
     }
-    if (pl.align) {
+    if (pl.align && p->alignment) {  // (a plan with band arrays of its own: their owner fills them)
         e = run(K_BAND, [&] {
             return launch_align(d, p->alignment, p->align_stride, p->align_blank, p->max_shift,
                                 carve<int>(ws, pl.off_mtmp), carve<int>(ws, pl.off_min), carve<int>(ws, pl.off_max),

@@ -38,7 +38,9 @@ struct Plan {
         off_llb, off_dyn, total;
 };
 
-RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl);
+// band: the plan holds the band arrays (min_s / max_s) although the problem has no alignment (mrnnt_path_*: the
+// hull of the given paths goes there)
+RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl, bool band = false);
 DevProblem make_dev(const mrnnt_problem *p, const Plan &pl, const void *ws);
 
 // The array at byte offset `off` of a workspace.

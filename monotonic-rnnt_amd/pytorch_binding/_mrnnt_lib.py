@@ -155,6 +155,12 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_cpu_posteriors": (i, [P, vp, vp, vp, vp, i64, vp, i64, i]),
         "mrnnt_sample": (i, [P, vp, i, ctypes.c_uint64, i64, vp, i64, vp, vp]),
         "mrnnt_cpu_sample": (i, [P, vp, i, ctypes.c_uint64, i64, vp, i64, vp, i]),
+        "mrnnt_path_workspace_size": (i, [P, i, ctypes.POINTER(sz)]),
+        "mrnnt_path_forward": (i, [P, vp, sz, vp, i, i64, vp, vp]),
+        "mrnnt_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, vp]),
+        "mrnnt_cpu_path_workspace_size": (i, [P, i, ctypes.POINTER(sz)]),
+        "mrnnt_cpu_path_forward": (i, [P, vp, sz, vp, i, i64, vp, i]),
+        "mrnnt_cpu_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, i]),
         "mrnnt_joint_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_forward": (i, [JP, vp, sz, vp, i, vp]),
         "mrnnt_joint_align": (i, [JP, vp, sz, vp, i64, vp, vp]),

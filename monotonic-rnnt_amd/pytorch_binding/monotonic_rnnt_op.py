@@ -268,12 +268,13 @@ class _Prepared:
         self.problem = p
         self.device = dev
 
-    def workspace(self) -> torch.Tensor:
+    def workspace(self, num_paths: int = 0) -> torch.Tensor:
+        """The call's workspace; num_paths > 0: the one of monotonic_rnnt_path_loss for that many paths."""
         p = self.problem
         # the plan also depends on V and the acts element type (whether the chase launch applies, and so whether the
         # workspace holds its ready flags) and on the device (its CU count bounds the chase)
         key = (self.on_gpu, self.alignment is not None, _L.load(), p.V, p.acts_dtype, str(self.device), p.pad_T,
-               p.pad_S1)
+               p.pad_S1, num_paths)
         if self.dyn:  # sized from bounds: the shapes of acts and labels
             key = key + (p.B, p.num_rows, p.label_stride)
             cache = _DYN_WS
@@ -282,7 +283,11 @@ class _Prepared:
         n = cache.get(key)
         if n is None:
             c = ctypes.c_size_t(0)
-            if self.on_gpu:  # the plan reads the CU count of the CURRENT device: make it this call's
+            if num_paths > 0:
+                size = _L.load().mrnnt_path_workspace_size if self.on_gpu else _L.load().mrnnt_cpu_path_workspace_size
+                with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
+                    _L.check(size(ctypes.byref(self.problem), num_paths, ctypes.byref(c)), "path_workspace_size")
+            elif self.on_gpu:  # the plan reads the CU count of the CURRENT device: make it this call's
                 with _on_device(self.device):
                     _L.check(_L.load().mrnnt_workspace_size(ctypes.byref(self.problem), ctypes.byref(c)),
                              "workspace_size")
@@ -601,6 +606,98 @@ def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_length
     return Samples(out, path_costs, costs)
 
 
+class MonotonicRNNTPathFunction(torch.autograd.Function):
+    """Scores of given alignments with their logit gradient (mrnnt_path_forward / mrnnt_path_backward and the
+    mrnnt_cpu_path_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, alignments,
+    blank_label=0) -> path_costs [B, K]. The upstream gradient of path_costs is the kernels' weights w[b, k]."""
+
+    @staticmethod
+    def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                label_lengths: torch.Tensor, alignments: torch.Tensor, blank_label: int = 0) -> torch.Tensor:
+        prep = _Prepared(acts, labels, input_lengths, label_lengths, None, 0, blank_label)
+        B, dev = prep.problem.B, prep.device
+        al = alignments.detach()
+        if al.device != dev or al.dtype != torch.int32:
+            al = al.to(dev, torch.int32)
+        if al.dim() != 3 or al.size(0) != B:
+            raise RuntimeError(f"monotonic_rnnt_path_loss: alignments must be [B = {B}, K, L], got {tuple(al.shape)}")
+        al = al.contiguous()
+        K, L = al.size(1), al.size(2)
+        if K < 1 or L < 1:
+            raise RuntimeError(f"monotonic_rnnt_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got {K}, {L}")
+        lib = _L.load()
+        ws = prep.workspace(num_paths=K)
+        costs = torch.empty((B, K), dtype=torch.float32, device=dev)
+        if not prep.on_gpu:
+            _L.check(lib.mrnnt_cpu_path_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
+                                                _ptr(costs), prep.num_threads), "mrnnt_cpu_path_forward")
+        else:
+            if prep.dyn:
+                check_lengths(sync=False)  # an earlier call's failed validation surfaces here (no wait)
+            with _on_device(dev):
+                _L.check(lib.mrnnt_path_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
+                                                _ptr(costs), prep.stream()), "mrnnt_path_forward")
+                if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
+                    torch.cuda.current_stream(dev).synchronize()
+                    check_lengths(sync=False)
+        if ctx.needs_input_grad[0]:
+            # acts is re-read by the gradient kernel on the rows the paths visit; the workspace holds den, the hull
+            # and the paths' validity
+            ctx.save_for_backward(acts, ws, al)
+            ctx.prep = prep
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        _, ws, al = ctx.saved_tensors
+        prep = ctx.prep
+        K, L = al.size(1), al.size(2)
+        w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
+        # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), as the loss's
+        grads = _GP.grads_like(prep.acts) if prep.on_gpu else torch.empty_like(prep.acts)
+        lib = _L.load()
+        if not prep.on_gpu:
+            _L.check(lib.mrnnt_cpu_path_backward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
+                                                 _ptr(w), _ptr(grads), prep.num_threads), "mrnnt_cpu_path_backward")
+        else:
+            with _on_device(prep.device):
+                _L.check(lib.mrnnt_path_backward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
+                                                 _ptr(w), _ptr(grads), prep.stream()), "mrnnt_path_backward")
+        return grads, None, None, None, None, None
+
+
+def monotonic_rnnt_path_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                             label_lengths: torch.Tensor, alignments: torch.Tensor,
+                             blank_label: int = 0) -> torch.Tensor:
+    """Differentiable scores of given alignments: path_costs[b, k] = -log p(alignment (b, k) | acts), the negative
+    log-probability of that one path through the lattice the loss sums over, with a gradient with respect to acts.
+    The missing piece between the read-outs (monotonic_rnnt_align, monotonic_rnnt_sample: not differentiable) and
+    training on their paths: Viterbi training (K = 1), risk-weighted / MWER / REINFORCE objectives over sampled paths
+    (the upstream gradient of each path cost may have either sign), latency penalties. One forward and one dense
+    gradient pass whatever K is:
+
+        s = monotonic_rnnt_sample(acts, labels, T, S, num_samples=8, seed=step)
+        pc = monotonic_rnnt_path_loss(acts, labels, T, S, s.alignments)          # [B, 8], differentiable
+        (risk(s.alignments).detach() * torch.softmax(-pc, 1)).sum().backward()
+
+    Args: acts, labels, input_lengths, label_lengths, blank_label as monotonic_rnnt_loss (CPU or GPU tensors; GPU: also
+    bfloat16 / float16 acts, the padded 4-D layout, GPU-resident lengths without a host read).
+        alignments: int [B, K, L] (returns [B, K]) or [B, L] (returns [B]), L >= every T_b, in the format
+                    monotonic_rnnt_align / monotonic_rnnt_sample return: entry t < T_b is blank_label or the label
+                    frame t emits; entries at t >= T_b are ignored.
+    A row that is no path of its utterance (a wrong or negative label, a -1 sentinel row, too few or too many labels)
+    costs +inf and gets no gradient whatever its upstream gradient is. A path through a -inf logit costs +inf; a NaN
+    logit on a visited row makes the visiting paths' costs and that row's gradient NaN and nothing else. Rows no valid
+    path with a non-zero upstream gradient visits have an exactly zero gradient and are not read. Costs and gradients
+    are bitwise reproducible. GPU-resident lengths that fail validation (T_b <= L included) make every value NaN and
+    surface through check_lengths() exactly as for the loss."""
+    if alignments.dim() == 2:
+        out = MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments.unsqueeze(1),
+                                              blank_label)
+        return out.squeeze(1)
+    return MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments, blank_label)
+
+
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
@@ -671,4 +768,5 @@ class _Ext:
 monotonic_rnnt_cpp = _Ext()
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
-           "monotonic_rnnt_align", "monotonic_rnnt_posteriors", "monotonic_rnnt_sample"]
+           "monotonic_rnnt_align", "monotonic_rnnt_posteriors", "monotonic_rnnt_sample",
+           "MonotonicRNNTPathFunction", "monotonic_rnnt_path_loss"]
