@@ -23,10 +23,6 @@ using namespace mrnnt;
 
 namespace {
 
-// Workgroups of 4 waves per CU of the log-softmax's persistent, work-stealing grid (device-resident lengths: the
-// host does not know the column count to launch one workgroup per column)
-constexpr int kStealGridPerCU = 16;
-
 RNNTStatus check_pointers(const mrnnt_problem *p) {
     if (!p->acts) return fail(RNNT_STATUS_INVALID_VALUE, "acts is null");
     if (!p->T_dev || !p->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
@@ -79,9 +75,7 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, floa
     const bool fused = pl.dyn && pl.B <= 64 && !pl.align && tuning().softmax_grid_per_cu <= 0 && tuning().dyn_fused;
     // the scattered order only matters where a workgroup walks several columns: the gradient's persistent grid
     // (the log-softmax's default is in order)
-    const int64_t scatter_above = ((tuning().col_scatter & 3) != 0 && !(tuning().col_xcd & 3))
-                                      ? (int64_t)streaming_grid(pl.cols, tuning().grad_grid_per_cu)
-                                      : INT64_MAX;
+    const int64_t scatter_above = grad_scatter_above(pl);
     if (!fused) {
         LatticeOpts o;
         o.scatter_above = scatter_above;
@@ -115,21 +109,18 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, floa
         if (e != hipSuccess) return fail_hip(e, "chase kernel");
         return RNNT_STATUS_SUCCESS;
     }
-    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
-    DevProblem ds = d;  // the log-softmax launch's view
-    ds.col_mul = column_order(pl, 1);
     if (fused) {
         // one workgroup per column at the lower bound of the column count (more columns are walked grid-stride)
-        grid = (int)std::max<int64_t>(1, std::min<int64_t>(min_cols(pl), 1 << 22));
+        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(min_cols(pl), 1 << 22));
+        DevProblem ds = d;  // the log-softmax launch's view
         ds.dyn_fused = 1;
         ds.col_mul = 0;
         if ((st = plan_in_launch(p, pl, scatter_above, &ds)) != RNNT_STATUS_SUCCESS) return st;
-    } else if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {  // one workgroup per column needs the column count
-        grid = streaming_grid(pl.cols, kStealGridPerCU);
-        ds.steal = grid < pl.cols;
+        e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
+        if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
+    } else if ((st = softmax_pass(pl, d, stream)) != RNNT_STATUS_SUCCESS) {
+        return st;
     }
-    e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
     e = timed(K_DP, stream, [&] { return launch_dp(d, pl.S_max, with_beta ? 1 : 0, costs_dev, stream); });
     if (e != hipSuccess) return fail_hip(e, "alpha/beta kernel");
     return RNNT_STATUS_SUCCESS;
@@ -172,9 +163,7 @@ RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *a
     if (st != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
     if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
-    if (out_stride < 1 || (!pl.dyn && out_stride < pl.T_max))
-        return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
-                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
+    if ((st = check_row_stride("alignment_out", out_stride, "input", pl.T_max, pl.dyn, 1)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, pl.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
     // the separate-kernel route of mrnnt_forward: setup, alignment band, log-softmax, then the Viterbi launch in the
@@ -182,18 +171,11 @@ RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *a
     LatticeOpts o;
     o.t_cap = out_stride;  // T_b <= out_stride joins the device validation
     if ((st = prepare_lattice(p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
-    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
-    DevProblem ds = d;  // the log-softmax launch's view, as mrnnt_forward's
-    ds.col_mul = column_order(pl, 1);
-    if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {
-        grid = streaming_grid(pl.cols, kStealGridPerCU);
-        ds.steal = grid < pl.cols;
-    }
-    hipError_t e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
+    if ((st = softmax_pass(pl, d, stream)) != RNNT_STATUS_SUCCESS) return st;
     // p->alignment may be alignment_out_dev itself: the band kernels above have consumed it (stream order) and the
     // Viterbi launch reads only the band arrays
-    e = timed(K_DP, stream, [&] { return launch_viterbi(d, pl.S_max, alignment_out_dev, out_stride, costs_dev, stream); });
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_viterbi(d, pl.S_max, alignment_out_dev, out_stride, costs_dev, stream); });
     if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
     return RNNT_STATUS_SUCCESS;
 }
@@ -205,21 +187,17 @@ RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *ws, float *blank
     RNNTStatus st = make_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     // with device lengths the kernels bound every write by the strides instead (and raise the status word)
-    if (emit_dev && (emit_stride < 0 || (!pl.dyn && emit_stride < pl.T_max)))
-        return fail(RNNT_STATUS_INVALID_VALUE, "emit row stride " + std::to_string(emit_stride) +
-                                                   " < max input length " + std::to_string(pl.dyn ? 0 : pl.T_max));
-    if (label_time_dev && (time_stride < 0 || (!pl.dyn && time_stride < pl.S_max)))
-        return fail(RNNT_STATUS_INVALID_VALUE, "label_time row stride " + std::to_string(time_stride) +
-                                                   " < max label length " + std::to_string(pl.dyn ? 0 : pl.S_max));
+    if (emit_dev && (st = check_row_stride("emit", emit_stride, "input", pl.T_max, pl.dyn, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
+    if (label_time_dev &&
+        (st = check_row_stride("label_time", time_stride, "label", pl.S_max, pl.dyn, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
     if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
     if (!p->T_dev || !p->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
     DevProblem d = make_dev(p, pl, ws);  // acts and labels are never read
     if (pl.dyn && (st = status_device_ptr(p, &d.status_host)) != RNNT_STATUS_SUCCESS) return st;
-    const PosteriorArgs a{blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride};
-    const int grid = streaming_grid((pl.cols + 15) / 16, 8);  // column workgroups: 16 waves, one column per wave
-    const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "posterior kernel");
-    return RNNT_STATUS_SUCCESS;
+    return posterior_readout(pl, d, {blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride},
+                             stream);
 }
 
 RNNTStatus mrnnt_sample(const mrnnt_problem *p, const void *ws, int num_samples, uint64_t seed, int64_t first_sample,
@@ -265,10 +243,7 @@ RNNTStatus make_path_plan(const mrnnt_problem *p, int num_paths, PathPlan *pp) {
 RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride) {
     if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
     // with device lengths T_b <= path_stride joins the device validation
-    if (path_stride < 1 || (!pl.dyn && path_stride < pl.T_max))
-        return fail(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(path_stride) +
-                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
-    return RNNT_STATUS_SUCCESS;
+    return check_row_stride("alignments", path_stride, "input", pl.T_max, pl.dyn, 1);
 }
 
 PathArgs path_args(const PathPlan &pp, void *ws, const int *alignments_dev, int num_paths, int64_t path_stride) {
@@ -310,23 +285,14 @@ RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes,
     DevProblem d = make_dev(p, pl, ws);  // d.min_s / d.max_s: the hull
     LatticeOpts o;
     o.t_cap = path_stride;
-    if ((tuning().col_scatter & 3) != 0 && !(tuning().col_xcd & 3))  // the gradient's column order, as mrnnt_forward
-        o.scatter_above = (int64_t)streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    o.scatter_above = grad_scatter_above(pl);  // the gradient's column order, as mrnnt_forward
     if ((st = prepare_lattice(p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
     PathArgs a = path_args(pp, ws, alignments_dev, num_paths, path_stride);
     a.costs = path_costs_dev;
     hipError_t e = timed(K_DP, stream, [&] { return launch_path_walk(d, a, pl.T_max, stream); });
     if (e != hipSuccess) return fail_hip(e, "path walk kernels");
     // the log-softmax over the hull rows: the launch of mrnnt_align, its alignment window the hull
-    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
-    DevProblem ds = d;
-    ds.col_mul = column_order(pl, 1);
-    if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {
-        grid = streaming_grid(pl.cols, kStealGridPerCU);
-        ds.steal = grid < pl.cols;
-    }
-    e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "log-softmax kernel");
+    if ((st = softmax_pass(pl, d, stream)) != RNNT_STATUS_SUCCESS) return st;
     if (path_costs_dev) {
         e = timed(K_DP, stream, [&] { return launch_path_score(d, a, stream); });
         if (e != hipSuccess) return fail_hip(e, "path score kernel");

@@ -251,6 +251,18 @@ inline int64_t acts_row(const CpuPlan &pl, int b, int t, int W) {
 
 int threads_of(int num_threads) { return num_threads > 0 ? num_threads : omp_get_max_threads(); }
 
+// Padding rows of the padded layout (t >= T_b, or s > S_b) of `out` ([B, pad_T, pad_S1, width], may be null): 0, as
+// the HIP path's pad-zero kernel. No-op for the packed layout.
+void zero_padding_rows(const mrnnt_problem *p, const CpuPlan &pl, float *out, int64_t width, int nt) {
+    if (!pl.pad_S1 || !out) return;
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
+        const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
+        const int64_t s0 = t < p->T_host[b] ? p->S_host[b] + 1 : 0;
+        std::fill(out + (pc * pl.pad_S1 + s0) * width, out + (pc + 1) * pl.pad_S1 * width, 0.0f);
+    }
+}
+
 // Alignment band (restrict_to_alignment, cpu_workspace_manager.h:207-224): with m(t) = aligned labels among
 // the first t frames, alpha(t, .) lives in [m(t+1-k), m(t+1+k)] (indices clamped to [0, T]).
 void band_utt(const int *al, int T, int k, int align_blank, int *min_s, int *max_s) {
@@ -591,17 +603,7 @@ RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *ws, const floa
         const int b = col_utt(pl, c);
         grad_column(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
     }
-    if (pl.pad_S1) {  // padding rows of the padded layout: 0 (the HIP path's pad-zero kernel)
-        const int V = pl.V;
-#pragma omp parallel for schedule(static) num_threads(nt)
-        for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
-            const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
-            const int T = p->T_host[b], S = p->S_host[b];
-            const int s0 = t < T ? S + 1 : 0;
-            float *g = grads + (pc * pl.pad_S1 + s0) * V;
-            std::fill(g, g + (pl.pad_S1 - s0) * V, 0.0f);
-        }
-    }
+    zero_padding_rows(p, pl, grads, pl.V, nt);
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -644,15 +646,7 @@ RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *b
     if (emit)
         for (int b = 0; b < pl.B; ++b)
             std::fill(emit + (int64_t)b * emit_stride + p->T_host[b], emit + (int64_t)(b + 1) * emit_stride, 0.0f);
-    if (pl.pad_S1 && (blank_post || label_post)) {  // padding rows of the padded layout: 0
-#pragma omp parallel for schedule(static) num_threads(nt)
-        for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
-            const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
-            const int64_t s0 = t < p->T_host[b] ? p->S_host[b] + 1 : 0;
-            for (float *out : {blank_post, label_post})
-                if (out) std::fill(out + pc * pl.pad_S1 + s0, out + (pc + 1) * pl.pad_S1, 0.0f);
-        }
-    }
+    for (float *out : {blank_post, label_post}) zero_padding_rows(p, pl, out, 1, nt);
     if (label_time) {
         std::vector<int64_t> lab_off(pl.B + 1, 0);  // (utterance, label) pairs, one sum along t each
         for (int b = 0; b < pl.B; ++b) lab_off[b + 1] = lab_off[b] + p->S_host[b];
@@ -910,15 +904,7 @@ RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_b
             if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)we;
         }
     }
-    if (pl.pad_S1) {  // padding rows of the padded layout: 0
-#pragma omp parallel for schedule(static) num_threads(nt)
-        for (int64_t pc = 0; pc < (int64_t)pl.B * pl.pad_T; ++pc) {
-            const int b = (int)(pc / pl.pad_T), t = (int)(pc % pl.pad_T);
-            const int s0 = t < p->T_host[b] ? p->S_host[b] + 1 : 0;
-            float *g = grads + (pc * pl.pad_S1 + s0) * V;
-            std::fill(g, g + (pl.pad_S1 - s0) * V, 0.0f);
-        }
-    }
+    zero_padding_rows(p, pl, grads, V, nt);
     return RNNT_STATUS_SUCCESS;
 }
 

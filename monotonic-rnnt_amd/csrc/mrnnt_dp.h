@@ -57,6 +57,26 @@ struct Utt {
 
 __device__ __forceinline__ Utt utt_of(const DevProblem &p, int b) { return Utt{p.T[b], p.S[b], p.row_off[b], p.col_off[b]}; }
 
+// NW waves x K cells per lane for the longest row W = S_max + 1 of a batch, for the per-step-barrier kernels
+// (recursion_kernel, viterbi_kernel): with SHORT one cell per lane on 1 / 2 / 4 waves up to 64 / 128 / 256 cells, then
+// one cell per lane on 8 waves up to 512 and 2 / 3 / 4 cells per lane on 8 waves. launch.go<K, NW>() launches; false: W
+// is beyond kMaxLabelsPlusOne.
+template <bool SHORT, class L>
+static bool launch_by_width(int W, const L &launch) {
+    if constexpr (SHORT) {
+        if (W <= 64) launch.template go<1, 1>();
+        else if (W <= 128) launch.template go<1, 2>();
+        else if (W <= 256) launch.template go<1, 4>();
+        if (W <= 256) return true;
+    }
+    if (W <= 512) launch.template go<1, 8>();
+    else if (W <= 1024) launch.template go<2, 8>();
+    else if (W <= 1536) launch.template go<3, 8>();
+    else if (W <= kMaxLabelsPlusOne) launch.template go<4, 8>();
+    else return false;
+    return true;
+}
+
 // The passes without a chase (mrnnt_recursion.hip): nothing gates the lp loads.
 struct NoChase {
     static constexpr bool kOn = false;

@@ -1,0 +1,196 @@
+// mrnnt_grad.h -- the dense logit-gradient streamers and their launch ladder, over a compile-time row policy P: the
+// loss gradient (LossRows, mrnnt_grad.hip) and the path-score gradient (PathRows, mrnnt_path.hip). P supplies
+//   Col, column()   what a lattice column sets up once: its band of rows with a gradient; zero(): the other rows' value
+//   Slot, stage()   a row's coefficients as they are staged in LDS, two buffers of 256 slots (a dead slot: the row is
+//                   stored as zero()), live()
+//   Coef, coef()    a live slot's coefficients as the formula takes them; row(): the same without staging (false:
+//                   not live), for the scalar kernel
+//   grad_vec(), grad()   the per-vector formula and its scalar twin
+//   launch_u()      which kernel a (U, NTL) pair takes;  kNtLoads: whether NTL is ever true
+// Everything else -- column walk, segments, barrier, load / store blocks, failed device lengths -- is here once.
+#pragma once
+
+#include "mrnnt_device.h"
+
+namespace mrnnt {
+
+constexpr int kGradSeg = 256;  // rows per work unit of the staged kernel: one per thread in phase A
+constexpr int kDeadRow = -2;   // label word of a staged row whose gradient is exactly zero (out of band or dead)
+
+// Staged-coefficient kernel (grad_variant 5, the default, and 6: 2 rows per wave). Work unit = a segment of up to 256
+// rows of one lattice column. Phase A: one row per thread, the row's coefficients (P::stage; the loss's row_coef reads
+// alpha/beta/den/lp as coalesced vectors along s, the two fp64 exps lane-parallel) go to an LDS slot.
+// Phase B: the waves stream the segment's rows; a row's acts loads wait only for one broadcast LDS read, not for
+// a chain of dependent scalar loads and fp64 math, so every wave keeps its row(s) of acts in flight. Two LDS
+// buffers alternate between work units: one barrier per unit.
+template <class IO, int U, int R, bool NTL, bool NTS, class P>
+__global__ __launch_bounds__(256) void grad_staged_kernel(DevProblem p, const float *__restrict__ scale,
+                                                          void *__restrict__ grads) {
+    if (!resolve_dyn(p)) {  // device-resident lengths failed validation: NaN gradients
+        fill_failed_grads<IO>(p, grads);
+        return;
+    }
+    typedef typename IO::V Vec;
+    typedef typename P::Slot Slot;
+    constexpr int SEG = kGradSeg;
+    __shared__ Slot coef[2][SEG];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int VL = p.V / IO::E;
+    const int blank = p.blank;
+    const Vec *__restrict__ av = reinterpret_cast<const Vec *>(p.acts);
+    Vec *__restrict__ gv = reinterpret_cast<Vec *>(grads);
+
+    Cursor cur;
+    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
+    int buf = 0;
+    for (int64_t ci = blockIdx.x; ci < p.num_cols; ci += gridDim.x) {
+        const int64_t c = visit_col(p, ci);
+        if (p.col_mul) cur.b = p.col_b[c];
+        else cur.advance(p.col_off, c);
+        const int b = cur.b;
+        const int T = p.T[b], S = p.S[b];
+        const int t = (int)(c - p.col_off[b]);
+        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
+        const int64_t arow = acts_col_base(p, b, t, rowc);
+        const typename P::Col col = P::column(p, b, c, t, T, S);
+        const float sc = scale ? scale[b * p.scale_stride] : 1.0f;  // upstream gradient of the utterance
+        const Vec zv = splat<IO>(P::zero(col, sc));
+        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
+
+        for (int seg = 0; seg <= S; seg += SEG, buf ^= 1) {
+            {  // phase A
+                const int s = seg + tid;
+                const Slot cf = P::stage(p, col, t, S, s, rowc, lab_b);
+                if (s <= S) coef[buf][tid] = cf;
+            }
+            __syncthreads();
+            const int n = min(SEG, S + 1 - seg);
+            for (int i = wave * R; i < n; i += 4 * R) {
+                Slot cf[R];
+                bool live[R], ok[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    ok[r] = i + r < n;
+                    cf[r] = coef[buf][ok[r] ? i + r : i];
+                    live[r] = ok[r] && P::live(cf[r]);
+                }
+                for (int base = 0; base < VL; base += 64 * U) {
+                    Vec x[R][U];
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int j = base + lane + 64 * u;
+                            if (live[r] && j < VL)
+                                x[r][u] = vload<NTL>(&av[(arow + seg + i + r) * (int64_t)VL + j]);
+                        }
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        if (!ok[r]) continue;
+                        decltype(auto) rc = P::coef(cf[r]);  // (a value or a reference to the slot, as P has it)
+#pragma unroll
+                        for (int u = 0; u < U; ++u) {
+                            const int j = base + lane + 64 * u;
+                            if (j >= VL) continue;
+                            const Vec g = live[r] ? P::template grad_vec<IO>(x[r][u], rc, j, blank, sc) : zv;
+                            vstore<NTS>(&gv[(arow + seg + i + r) * (int64_t)VL + j], g);
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// Scalar path (any V, any alignment): one row per wave, lanes stride over v.
+template <class IO, class P>
+__global__ __launch_bounds__(256) void grad_scalar_kernel(DevProblem p, const float *__restrict__ scale,
+                                                          void *__restrict__ grads) {
+    if (!resolve_dyn(p)) {  // device-resident lengths failed validation: NaN gradients
+        fill_failed_grads<IO>(p, grads);
+        return;
+    }
+    typedef typename IO::S Sc;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int V = p.V;
+    const int blank = p.blank;
+    const Sc *__restrict__ acts = reinterpret_cast<const Sc *>(p.acts);
+    Sc *__restrict__ gs = reinterpret_cast<Sc *>(grads);
+    Cursor cur;
+    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
+    for (int64_t c = blockIdx.x; c < p.num_cols; c += gridDim.x) {
+        cur.advance(p.col_off, c);
+        const int b = cur.b;
+        const int T = p.T[b], S = p.S[b];
+        const int t = (int)(c - p.col_off[b]);
+        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
+        const int64_t arow = acts_col_base(p, b, t, rowc);
+        const typename P::Col col = P::column(p, b, c, t, T, S);
+        const float sc = scale ? scale[b * p.scale_stride] : 1.0f;
+        const Sc zs = IO::from_f(P::zero(col, sc));
+        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
+        for (int s = wave; s <= S; s += 4) {
+            Sc *__restrict__ g = gs + (arow + s) * (int64_t)V;
+            typename P::Coef rc;
+            if (!P::row(p, col, t, S, s, rowc, lab_b, rc)) {
+                for (int v = lane; v < V; v += 64) g[v] = zs;
+                continue;
+            }
+            const Sc *__restrict__ z = acts + (arow + s) * (int64_t)V;
+            for (int v = lane; v < V; v += 64) g[v] = IO::from_f(P::grad(IO::to_f(z[v]), v, rc, blank, sc));
+        }
+    }
+}
+
+template <class IO>
+static bool vec_ok(const DevProblem &p, const void *grads) {
+    return (p.V % IO::E) == 0 && (reinterpret_cast<uintptr_t>(p.acts) % 16) == 0 &&
+           (reinterpret_cast<uintptr_t>(grads) % 16) == 0;
+}
+
+// rows per wave of the staged kernel for U vectors per lane: >= 4 KiB of acts in flight per wave
+constexpr int staged_rows(int U) { return U == 4 ? 1 : (U == 2 ? 2 : 4); }
+
+// U = 16-byte vectors per lane per chunk: 4 KiB chunks for rows of >= 192 vectors, 2 KiB for >= 96, else 1 KiB
+template <class P, class IO, bool NTL, bool NTS>
+static void launch_vec(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
+    const int VL = p.V / IO::E;
+    if (VL >= 192) P::template launch_u<IO, NTL, NTS, 4>(p, scale, grads, grid, stream);
+    else if (VL >= 96) P::template launch_u<IO, NTL, NTS, 2>(p, scale, grads, grid, stream);
+    else P::template launch_u<IO, NTL, NTS, 1>(p, scale, grads, grid, stream);
+}
+
+template <class P, class IO>
+static void launch_io(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
+    if (!vec_ok<IO>(p, grads)) {
+        grad_scalar_kernel<IO, P><<<grid, 256, 0, stream>>>(p, scale, grads);
+        return;
+    }
+    const bool nts = tuning().nt_store != 0;
+    if constexpr (P::kNtLoads) {  // the policy's acts loads go nontemporal by size (nt_acts_loads)
+        if (nt_acts_loads(p, sizeof(typename IO::S))) {
+            if (nts) launch_vec<P, IO, true, true>(p, scale, grads, grid, stream);
+            else launch_vec<P, IO, true, false>(p, scale, grads, grid, stream);
+            return;
+        }
+    }
+    if (nts) launch_vec<P, IO, false, true>(p, scale, grads, grid, stream);
+    else launch_vec<P, IO, false, false>(p, scale, grads, grid, stream);
+}
+
+template <class P>
+static hipError_t launch_grad_rows(const DevProblem &p, int elem, const float *scale, void *grads, int grid,
+                                   hipStream_t stream) {
+    switch (elem) {
+        case ELEM_F32: launch_io<P, IoF32>(p, scale, grads, grid, stream); break;
+        case ELEM_BF16: launch_io<P, IoBF16>(p, scale, grads, grid, stream); break;
+        case ELEM_F16: launch_io<P, IoF16>(p, scale, grads, grid, stream); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace mrnnt

@@ -7,30 +7,78 @@
 // element it is one fma + one v_exp_f32 (+ a select for the <= 2 special columns) in fp32 registers,
 // then one conversion to the output element type. Out-of-band lattice rows store 0 * grad_scale (the
 // reference's backward multiplies its zero rows by grad_output; NaN when ll = -inf, zero_row_value); padding
-// rows of the padded layout store 0 (launch_pad_zero).
+// rows of the padded layout store 0 (launch_pad_zero). The staged and the scalar kernel are the shared streamers of
+// mrnnt_grad.h over the row policy LossRows below.
 #include <algorithm>
 
-#include "mrnnt_device.h"
+#include "mrnnt_grad.h"
 
 namespace mrnnt {
 
-template <class IO>
-__device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const RowCoef &rc, int j, int blank,
-                                                   float sc) {
-    constexpr int E = IO::E;
-    float x[E];
-    IO::unpack(xv, x);
-    const int v0 = j * E;
-    const int db = blank - v0;
-    const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        float g = fast_exp2(fmaf(x[i], kLog2e, rc.c2));
-        g -= (db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f);
-        x[i] = g * sc;
+// The loss's rows for the shared streamers (mrnnt_grad.h): band = the monotonic band of the column, a row's staged
+// coefficients {c2, cb, ce, label | kDeadRow} from row_coef, the other rows zero_row_value.
+struct LossRows {
+    struct Col {
+        int T, lo, hi;
+        double ll;
+    };
+    static __device__ __forceinline__ Col column(const DevProblem &p, int b, int64_t, int t, int T, int S) {
+        return Col{T, max(0, t - (T - S)), min(t, S), p.ll[b]};
     }
-    return IO::pack(x);
-}
+    static __device__ __forceinline__ float zero(const Col &col, float sc) { return zero_row_value(col.ll, sc); }
+
+    typedef RowCoef Coef;
+    // false: the row is stored as zero() (out of band, or dead)
+    static __device__ __forceinline__ bool row(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                               const int *lab_b, Coef &rc) {
+        const bool inb = s >= col.lo && s <= col.hi;
+        if (inb) rc = row_coef(p, t, col.T, S, s, rowc + s, col.ll, lab_b);
+        return inb && rc.live;
+    }
+
+    typedef float4 Slot;
+    static __device__ __forceinline__ Slot stage(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                                 const int *lab_b) {
+        Slot cf = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(kDeadRow));
+        if (s >= col.lo && s <= col.hi) {
+            const RowCoef rc = row_coef(p, t, col.T, S, s, rowc + s, col.ll, lab_b);
+            if (rc.live) cf = make_float4(rc.c2, rc.cb, rc.ce, __int_as_float(rc.lab));
+        }
+        return cf;
+    }
+    static __device__ __forceinline__ bool live(const Slot &cf) { return __float_as_int(cf.w) != kDeadRow; }
+    static __device__ __forceinline__ Coef coef(const Slot &cf) {
+        return RowCoef{cf.x, cf.y, cf.z, __float_as_int(cf.w), true};
+    }
+
+    template <class IO>
+    static __device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const RowCoef &rc, int j,
+                                                              int blank, float sc) {
+        constexpr int E = IO::E;
+        float x[E];
+        IO::unpack(xv, x);
+        const int v0 = j * E;
+        const int db = blank - v0;
+        const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            float g = fast_exp2(fmaf(x[i], kLog2e, rc.c2));
+            g -= (db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f);
+            x[i] = g * sc;
+        }
+        return IO::pack(x);
+    }
+    static __device__ __forceinline__ float grad(float z, int v, const RowCoef &rc, int blank, float sc) {
+        float g = fast_exp2(fmaf(z, kLog2e, rc.c2));
+        if (v == blank) g -= rc.cb;
+        else if (v == rc.lab) g -= rc.ce;
+        return g * sc;
+    }
+
+    static constexpr bool kNtLoads = true;
+    template <class IO, bool NTL, bool NTS, int U>
+    static void launch_u(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream);
+};
 
 // Column-walking kernel with per-row coefficients (grad_variant 0 / 2): workgroups walk lattice columns, the
 // four waves take rows s (R at a time), lanes take 16-byte vectors of the row, U per lane per chunk.
@@ -95,102 +143,9 @@ __global__ __launch_bounds__(256) void grad_kernel(DevProblem p, const float *__
                     for (int u = 0; u < U; ++u) {
                         const int j = base + lane + 64 * u;
                         if (!ok[r] || j >= VL) continue;
-                        const Vec g = inb[r] ? grad_vec<IO>(x[r][u], rc[r], j, blank, sc) : zv;
+                        const Vec g = inb[r] ? LossRows::grad_vec<IO>(x[r][u], rc[r], j, blank, sc) : zv;
                         vstore<NTS>(&gv[(arow + s + r) * (int64_t)VL + j], g);
                     }
-            }
-        }
-    }
-}
-
-// Staged-coefficient kernel (grad_variant 5, the default, and 6: 2 rows per wave). Work unit = a segment of up to 256
-// rows of one lattice column. Phase A: one row per thread, the row's coefficients (row_coef: alpha/beta/den/lp
-// read as coalesced vectors along s, the two fp64 exps lane-parallel) go to an LDS slot {c2, cb, ce, label|dead}.
-// Phase B: the waves stream the segment's rows; a row's acts loads wait only for one broadcast LDS read, not for
-// a chain of dependent scalar loads and fp64 math, so every wave keeps its row(s) of acts in flight. Two LDS
-// buffers alternate between work units: one barrier per unit.
-template <class IO, int U, int R, bool NTL, bool NTS>
-__global__ __launch_bounds__(256) void grad_staged_kernel(DevProblem p, const float *__restrict__ scale,
-                                                          void *__restrict__ grads) {
-    if (!resolve_dyn(p)) {  // device-resident lengths failed validation: NaN gradients
-        fill_failed_grads<IO>(p, grads);
-        return;
-    }
-    typedef typename IO::V Vec;
-    constexpr int SEG = 256;
-    constexpr int DEAD = -2;  // label slot of a row whose gradient is exactly zero (out of band or dead)
-    __shared__ float4 coef[2][SEG];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int VL = p.V / IO::E;
-    const int blank = p.blank;
-    const Vec *__restrict__ av = reinterpret_cast<const Vec *>(p.acts);
-    Vec *__restrict__ gv = reinterpret_cast<Vec *>(grads);
-
-    Cursor cur;
-    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
-    int buf = 0;
-    for (int64_t ci = blockIdx.x; ci < p.num_cols; ci += gridDim.x) {
-        const int64_t c = visit_col(p, ci);
-        if (p.col_mul) cur.b = p.col_b[c];
-        else cur.advance(p.col_off, c);
-        const int b = cur.b;
-        const int T = p.T[b], S = p.S[b];
-        const int t = (int)(c - p.col_off[b]);
-        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
-        const int64_t arow = acts_col_base(p, b, t, rowc);
-        const int lo = max(0, t - (T - S));
-        const int hi = min(t, S);
-        const double ll = p.ll[b];
-        const float sc = scale ? scale[b * p.scale_stride] : 1.0f;
-        const Vec zv = splat<IO>(zero_row_value(ll, sc));
-        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
-
-        for (int seg = 0; seg <= S; seg += SEG, buf ^= 1) {
-            {  // phase A
-                const int s = seg + tid;
-                float4 cf = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(DEAD));
-                if (s >= lo && s <= hi) {
-                    const RowCoef rc = row_coef(p, t, T, S, s, rowc + s, ll, lab_b);
-                    if (rc.live) cf = make_float4(rc.c2, rc.cb, rc.ce, __int_as_float(rc.lab));
-                }
-                if (s <= S) coef[buf][tid] = cf;
-            }
-            __syncthreads();
-            const int n = min(SEG, S + 1 - seg);
-            for (int i = wave * R; i < n; i += 4 * R) {
-                float4 cf[R];
-                bool live[R], ok[R];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    ok[r] = i + r < n;
-                    cf[r] = coef[buf][ok[r] ? i + r : i];
-                    live[r] = ok[r] && __float_as_int(cf[r].w) != DEAD;
-                }
-                for (int base = 0; base < VL; base += 64 * U) {
-                    Vec x[R][U];
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int j = base + lane + 64 * u;
-                            if (live[r] && j < VL)
-                                x[r][u] = vload<NTL>(&av[(arow + seg + i + r) * (int64_t)VL + j]);
-                        }
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        if (!ok[r]) continue;
-                        const RowCoef rc{cf[r].x, cf[r].y, cf[r].z, __float_as_int(cf[r].w), true};
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int j = base + lane + 64 * u;
-                            if (j >= VL) continue;
-                            const Vec g = live[r] ? grad_vec<IO>(x[r][u], rc, j, blank, sc) : zv;
-                            vstore<NTS>(&gv[(arow + seg + i + r) * (int64_t)VL + j], g);
-                        }
-                    }
-                }
             }
         }
     }
@@ -246,57 +201,7 @@ __global__ __launch_bounds__(256) void grad_rows_kernel(DevProblem p, const floa
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int j = base + lane + 64 * u;
-                if (j < VL) vstore<NTS>(out + j, grad_vec<IO>(x[u], rc, j, blank, sc));
-            }
-        }
-    }
-}
-
-// Scalar path (any V, any alignment): one row per wave, lanes stride over v.
-template <class IO>
-__global__ __launch_bounds__(256) void grad_scalar_kernel(DevProblem p, const float *__restrict__ scale,
-                                                          void *__restrict__ grads) {
-    if (!resolve_dyn(p)) {  // device-resident lengths failed validation: NaN gradients
-        fill_failed_grads<IO>(p, grads);
-        return;
-    }
-    typedef typename IO::S Sc;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int V = p.V;
-    const int blank = p.blank;
-    const Sc *__restrict__ acts = reinterpret_cast<const Sc *>(p.acts);
-    Sc *__restrict__ gs = reinterpret_cast<Sc *>(grads);
-    Cursor cur;
-    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
-    for (int64_t c = blockIdx.x; c < p.num_cols; c += gridDim.x) {
-        cur.advance(p.col_off, c);
-        const int b = cur.b;
-        const int T = p.T[b], S = p.S[b];
-        const int t = (int)(c - p.col_off[b]);
-        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
-        const int64_t arow = acts_col_base(p, b, t, rowc);
-        const int lo = max(0, t - (T - S));
-        const int hi = min(t, S);
-        const double ll = p.ll[b];
-        const float sc = scale ? scale[b * p.scale_stride] : 1.0f;
-        const Sc zs = IO::from_f(zero_row_value(ll, sc));
-        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
-        for (int s = wave; s <= S; s += 4) {
-            Sc *__restrict__ g = gs + (arow + s) * (int64_t)V;
-            RowCoef rc;
-            const bool inb = s >= lo && s <= hi;
-            if (inb) rc = row_coef(p, t, T, S, s, rowc + s, ll, lab_b);
-            if (!inb || !rc.live) {
-                for (int v = lane; v < V; v += 64) g[v] = zs;
-                continue;
-            }
-            const Sc *__restrict__ z = acts + (arow + s) * (int64_t)V;
-            for (int v = lane; v < V; v += 64) {
-                float gv = fast_exp2(fmaf(IO::to_f(z[v]), kLog2e, rc.c2));
-                if (v == blank) gv -= rc.cb;
-                else if (v == rc.lab) gv -= rc.ce;
-                g[v] = IO::from_f(gv * sc);
+                if (j < VL) vstore<NTS>(out + j, LossRows::grad_vec<IO>(x[u], rc, j, blank, sc));
             }
         }
     }
@@ -370,20 +275,14 @@ __global__ __launch_bounds__(256) void pad_zero_kernel(DevProblem p, void *__res
     }
 }
 
-template <class IO>
-static bool vec_ok(const DevProblem &p, const void *grads) {
-    return (p.V % IO::E) == 0 && (reinterpret_cast<uintptr_t>(p.acts) % 16) == 0 &&
-           (reinterpret_cast<uintptr_t>(grads) % 16) == 0;
-}
-
 template <class IO, bool NTL, bool NTS, int U>
-static void launch_u(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
-    constexpr int RD = U == 4 ? 1 : (U == 2 ? 2 : 4);  // rows per wave: >= 4 KiB of acts in flight per wave
+void LossRows::launch_u(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
+    constexpr int RD = staged_rows(U);
     if constexpr (!kVariants) {  // the product library: the tuned default (grad_variant 5) only
         if constexpr (U == 1 && NTL)
             grad_kernel<IO, U, 2, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
         else
-            grad_staged_kernel<IO, U, RD, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
+            grad_staged_kernel<IO, U, RD, NTL, NTS, LossRows><<<grid, 256, 0, stream>>>(p, scale, grads);
     } else {
         const int variant = tuning().grad_variant;
         if (variant == 3 && p.pad_S1 == 0)
@@ -395,42 +294,14 @@ static void launch_u(const DevProblem &p, const float *scale, void *grads, int g
             // loads: 50.0 us against 56.3 for 4 rows and 60.2 staged, profiles/r02/kbench/grad_short_rows_c2*.json)
             grad_kernel<IO, U, 2, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
         else if (variant == 6)
-            grad_staged_kernel<IO, U, 2, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
+            grad_staged_kernel<IO, U, 2, NTL, NTS, LossRows><<<grid, 256, 0, stream>>>(p, scale, grads);
         else  // (1 KiB rows resident in the Infinity Cache, configs[1]: staged, 4 rows per wave, 40.2 against 47.6 us)
-            grad_staged_kernel<IO, U, RD, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
+            grad_staged_kernel<IO, U, RD, NTL, NTS, LossRows><<<grid, 256, 0, stream>>>(p, scale, grads);
     }
-}
-
-// U = 16-byte vectors per lane per chunk: 4 KiB chunks for rows of >= 192 vectors, 2 KiB for >= 96, else 1 KiB
-template <class IO, bool NTL, bool NTS>
-static void launch_vec(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
-    const int VL = p.V / IO::E;
-    if (VL >= 192) launch_u<IO, NTL, NTS, 4>(p, scale, grads, grid, stream);
-    else if (VL >= 96) launch_u<IO, NTL, NTS, 2>(p, scale, grads, grid, stream);
-    else launch_u<IO, NTL, NTS, 1>(p, scale, grads, grid, stream);
-}
-
-template <class IO>
-static void launch_io(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
-    if (!vec_ok<IO>(p, grads)) {
-        grad_scalar_kernel<IO><<<grid, 256, 0, stream>>>(p, scale, grads);
-        return;
-    }
-    const bool ntl = nt_acts_loads(p, sizeof(typename IO::S)), nts = tuning().nt_store != 0;
-    if (ntl && nts) launch_vec<IO, true, true>(p, scale, grads, grid, stream);
-    else if (ntl) launch_vec<IO, true, false>(p, scale, grads, grid, stream);
-    else if (nts) launch_vec<IO, false, true>(p, scale, grads, grid, stream);
-    else launch_vec<IO, false, false>(p, scale, grads, grid, stream);
 }
 
 hipError_t launch_grad(const DevProblem &p, int elem, const float *scale, void *grads, int grid, hipStream_t stream) {
-    switch (elem) {
-        case ELEM_F32: launch_io<IoF32>(p, scale, grads, grid, stream); break;
-        case ELEM_BF16: launch_io<IoBF16>(p, scale, grads, grid, stream); break;
-        case ELEM_F16: launch_io<IoF16>(p, scale, grads, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_grad_rows<LossRows>(p, elem, scale, grads, grid, stream);
 }
 
 hipError_t launch_pad_zero(const DevProblem &p, int elem, void *grads, hipStream_t stream) {

@@ -192,9 +192,8 @@ RNNTStatus mrnnt_joint_align(const mrnnt_joint_problem *jp, void *ws, size_t ws_
     RNNTStatus st = make_joint_plan(jp, &jl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
-    if (out_stride < jl.base.T_max)
-        return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
-                                                   " < max input length " + std::to_string(jl.base.T_max));
+    if ((st = check_row_stride("alignment_out", out_stride, "input", jl.base.T_max, false, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
     DevProblem d;
     if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, out_stride, stream, &d)) != RNNT_STATUS_SUCCESS) return st;
     // jp->alignment may be alignment_out_dev itself: the band kernels have consumed it (stream order), the joint
@@ -217,12 +216,11 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws,
         return fail(RNNT_STATUS_INVALID_VALUE, "posterior grid [" + std::to_string(grid_T) + ", " +
                                                    std::to_string(grid_S1) + "] smaller than [max T, max S + 1] = [" +
                                                    std::to_string(pl.T_max) + ", " + std::to_string(pl.S_max + 1) + "]");
-    if (emit_dev && emit_stride < pl.T_max)
-        return fail(RNNT_STATUS_INVALID_VALUE, "emit row stride " + std::to_string(emit_stride) +
-                                                   " < max input length " + std::to_string(pl.T_max));
-    if (label_time_dev && time_stride < pl.S_max)
-        return fail(RNNT_STATUS_INVALID_VALUE, "label_time row stride " + std::to_string(time_stride) +
-                                                   " < max label length " + std::to_string(pl.S_max));
+    if (emit_dev && (st = check_row_stride("emit", emit_stride, "input", pl.T_max, false, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
+    if (label_time_dev &&
+        (st = check_row_stride("label_time", time_stride, "label", pl.S_max, false, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
     if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
     if (!jp->T_dev || !jp->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
     const mrnnt_problem p = base_problem(jp);
@@ -233,11 +231,8 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws,
         d.pad_T = grid_T;
         d.pad_S1 = grid_S1;
     }
-    const PosteriorArgs a{blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride};
-    const int grid = streaming_grid((pl.cols + 15) / 16, 8);  // as mrnnt_posteriors
-    const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "posterior kernel");
-    return RNNT_STATUS_SUCCESS;
+    return posterior_readout(pl, d, {blank_post_dev, label_post_dev, emit_dev, emit_stride, label_time_dev, time_stride},
+                             stream);
 }
 
 RNNTStatus mrnnt_joint_sample(const mrnnt_joint_problem *jp, const void *ws, int num_samples, uint64_t seed,

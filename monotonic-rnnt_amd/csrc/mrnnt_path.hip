@@ -16,8 +16,8 @@
 //   coef  (one wave per frame block)    Wb / We (the workspace's alpha / beta arrays) zeroed over the hull, then
 //                                       w[b, k] added in ascending k, lane = frame: a lane's rows are its own column's,
 //                                       so no atomics and a fixed order
-//   grad                                the staged gradient kernel of mrnnt_grad.hip with the coefficient phase reading
-//                                       Wb / We / den; "in band" = in the hull, "live" = Wb != 0 || We != 0
+//   grad                                the gradient streamers of mrnnt_grad.h over PathRows: coefficients from Wb /
+//                                       We / den; "in band" = in the hull, "live" = Wb != 0 || We != 0
 //
 // The hull in the band arrays. The log-softmax reduces, in column c = (b, t), the rows
 //   [min(min_s[c] - 1, min_s[c-1]), max(max_s[c], max_s[c-1])]        (align_window, mrnnt_device.h; t = 0: with 0)
@@ -27,7 +27,7 @@
 // frame 0, so such an utterance has that one row reduced; nothing reads the result.
 #include <algorithm>
 
-#include "mrnnt_device.h"
+#include "mrnnt_grad.h"
 
 namespace mrnnt {
 
@@ -184,197 +184,80 @@ __global__ __launch_bounds__(256) void path_coef_kernel(DevProblem p, PathArgs a
 
 // ---- gradient ------------------------------------------------------------------------------------------------------
 
-struct PathCoef {
-    float c2;    // den * log2(e)
-    float wocc;  // Wb + We (signed; 0 on cancellation)
-    float cb;    // Wb
-    float ce;    // We
-    int lab;     // label(s), -1 for s == S / label == blank / out of range; kDead: the row is stored as zeros
-};
-constexpr int kDead = -2;
-
-__device__ __forceinline__ PathCoef path_coef(const DevProblem &p, int S, int s, int64_t row,
-                                              const int *__restrict__ lab_b) {
-    PathCoef c{0.0f, 0.0f, 0.0f, 0.0f, kDead};
-    const double wb = p.alpha[row], we = p.beta[row];
-    if (!(wb != 0.0 || we != 0.0)) return c;
-    c.c2 = p.den[row] * kLog2e;
-    c.wocc = (float)(wb + we);
-    c.cb = (float)wb;
-    c.ce = (float)we;
-    const int lab = (s < S) ? lab_b[s] : -1;
-    c.lab = (lab == p.blank || (unsigned)lab >= (unsigned)p.V) ? -1 : lab;
-    return c;
-}
-
-template <class IO>
-__device__ __forceinline__ typename IO::V path_grad_vec(const typename IO::V &xv, const PathCoef &rc, int j, int blank) {
-    constexpr int E = IO::E;
-    float x[E];
-    IO::unpack(xv, x);
-    const int v0 = j * E;
-    const int db = blank - v0;
-    const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        const float g = rc.wocc * fast_exp2(fmaf(x[i], kLog2e, rc.c2));
-        x[i] = g - ((db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f));
+// The path scores' rows for the shared streamers (mrnnt_grad.h): band = the hull of the column, a row's staged
+// coefficients from Wb / We / den, the other rows plain zeros; no upstream scale (the weights are in Wb / We).
+struct PathRows {
+    struct Col {
+        int lo, hi;
+    };
+    static __device__ __forceinline__ Col column(const DevProblem &p, int, int64_t c, int, int, int S) {
+        return Col{p.min_s[c] - 1, min(p.max_s[c], S)};
     }
-    return IO::pack(x);
-}
+    static __device__ __forceinline__ float zero(const Col &, float) { return 0.0f; }
 
-// The staged-coefficient kernel of mrnnt_grad.hip (work unit: a segment of up to 256 rows of one lattice column; phase
-// A one row per thread into an LDS slot, phase B the waves stream the rows), with phase A reading Wb / We / den.
-template <class IO, int U, int R, bool NTL, bool NTS>
-__global__ __launch_bounds__(256) void path_grad_staged_kernel(DevProblem p, void *__restrict__ grads) {
-    if (!resolve_dyn(p)) {  // device-resident lengths failed validation: NaN gradients
-        fill_failed_grads<IO>(p, grads);
-        return;
+    struct Slot {
+        float c2;    // den * log2(e)
+        float wocc;  // Wb + We (signed; 0 on cancellation)
+        float cb;    // Wb
+        float ce;    // We
+        int lab;     // label(s), -1 for s == S / label == blank / out of range; kDeadRow: the row is stored as zeros
+    };
+    typedef Slot Coef;
+    // (as the loss's row_coef: nothing of the row is read before it is known to be in the hull)
+    static __device__ __forceinline__ Slot stage(const DevProblem &p, const Col &col, int, int S, int s, int64_t rowc,
+                                                 const int *lab_b) {
+        Slot c{0.0f, 0.0f, 0.0f, 0.0f, kDeadRow};
+        if (!(s >= col.lo && s <= col.hi)) return c;
+        const int64_t row = rowc + s;
+        const double wb = p.alpha[row], we = p.beta[row];
+        if (!(wb != 0.0 || we != 0.0)) return c;
+        c.c2 = p.den[row] * kLog2e;
+        c.wocc = (float)(wb + we);
+        c.cb = (float)wb;
+        c.ce = (float)we;
+        const int lab = (s < S) ? lab_b[s] : -1;
+        c.lab = (lab == p.blank || (unsigned)lab >= (unsigned)p.V) ? -1 : lab;
+        return c;
     }
-    typedef typename IO::V Vec;
-    constexpr int SEG = 256;
-    __shared__ float4 coef[2][SEG];
-    __shared__ int clab[2][SEG];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int VL = p.V / IO::E;
-    const int blank = p.blank;
-    const Vec *__restrict__ av = reinterpret_cast<const Vec *>(p.acts);
-    Vec *__restrict__ gv = reinterpret_cast<Vec *>(grads);
-    const Vec zv = splat<IO>(0.0f);
+    static __device__ __forceinline__ bool row(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                               const int *lab_b, Coef &c) {
+        c = stage(p, col, t, S, s, rowc, lab_b);
+        return live(c);
+    }
+    static __device__ __forceinline__ bool live(const Slot &c) { return c.lab != kDeadRow; }
+    static __device__ __forceinline__ const Coef &coef(const Slot &c) { return c; }
 
-    Cursor cur;
-    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
-    int buf = 0;
-    for (int64_t ci = blockIdx.x; ci < p.num_cols; ci += gridDim.x) {
-        const int64_t c = visit_col(p, ci);
-        if (p.col_mul) cur.b = p.col_b[c];
-        else cur.advance(p.col_off, c);
-        const int b = cur.b;
-        const int S = p.S[b];
-        const int t = (int)(c - p.col_off[b]);
-        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
-        const int64_t arow = acts_col_base(p, b, t, rowc);
-        const int lo = p.min_s[c] - 1, hi = min(p.max_s[c], S);
-        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
-
-        for (int seg = 0; seg <= S; seg += SEG, buf ^= 1) {
-            {  // phase A
-                const int s = seg + tid;
-                PathCoef cf{0.0f, 0.0f, 0.0f, 0.0f, kDead};
-                if (s >= lo && s <= hi) cf = path_coef(p, S, s, rowc + s, lab_b);
-                if (s <= S) {
-                    coef[buf][tid] = make_float4(cf.c2, cf.wocc, cf.cb, cf.ce);
-                    clab[buf][tid] = cf.lab;
-                }
-            }
-            __syncthreads();
-            const int n = min(SEG, S + 1 - seg);
-            for (int i = wave * R; i < n; i += 4 * R) {
-                PathCoef rc[R];
-                bool live[R], ok[R];
+    template <class IO>
+    static __device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const Slot &rc, int j, int blank,
+                                                              float) {
+        constexpr int E = IO::E;
+        float x[E];
+        IO::unpack(xv, x);
+        const int v0 = j * E;
+        const int db = blank - v0;
+        const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    ok[r] = i + r < n;
-                    const int at = ok[r] ? i + r : i;
-                    const float4 f = coef[buf][at];
-                    rc[r] = PathCoef{f.x, f.y, f.z, f.w, clab[buf][at]};
-                    live[r] = ok[r] && rc[r].lab != kDead;
-                }
-                for (int base = 0; base < VL; base += 64 * U) {
-                    Vec x[R][U];
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int j = base + lane + 64 * u;
-                            if (live[r] && j < VL)
-                                x[r][u] = vload<NTL>(&av[(arow + seg + i + r) * (int64_t)VL + j]);
-                        }
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        if (!ok[r]) continue;
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            const int j = base + lane + 64 * u;
-                            if (j >= VL) continue;
-                            const Vec g = live[r] ? path_grad_vec<IO>(x[r][u], rc[r], j, blank) : zv;
-                            vstore<NTS>(&gv[(arow + seg + i + r) * (int64_t)VL + j], g);
-                        }
-                    }
-                }
-            }
+        for (int i = 0; i < E; ++i) {
+            const float g = rc.wocc * fast_exp2(fmaf(x[i], kLog2e, rc.c2));
+            x[i] = g - ((db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f));
         }
+        return IO::pack(x);
     }
-}
+    static __device__ __forceinline__ float grad(float z, int v, const Slot &rc, int blank, float) {
+        float g = rc.wocc * fast_exp2(fmaf(z, kLog2e, rc.c2));
+        if (v == blank) g -= rc.cb;
+        else if (v == rc.lab) g -= rc.ce;
+        return g;
+    }
 
-// Scalar path (any V, any alignment): one row per wave, lanes stride over v.
-template <class IO>
-__global__ __launch_bounds__(256) void path_grad_scalar_kernel(DevProblem p, void *__restrict__ grads) {
-    if (!resolve_dyn(p)) {
-        fill_failed_grads<IO>(p, grads);
-        return;
-    }
-    typedef typename IO::S Sc;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int V = p.V;
-    const int blank = p.blank;
-    const Sc *__restrict__ acts = reinterpret_cast<const Sc *>(p.acts);
-    Sc *__restrict__ gs = reinterpret_cast<Sc *>(grads);
-    const Sc zs = IO::from_f(0.0f);
-    Cursor cur;
-    cur.b = blockIdx.x < p.num_cols ? p.col_b[blockIdx.x] : 0;
-    for (int64_t c = blockIdx.x; c < p.num_cols; c += gridDim.x) {
-        cur.advance(p.col_off, c);
-        const int b = cur.b;
-        const int S = p.S[b];
-        const int t = (int)(c - p.col_off[b]);
-        const int64_t rowc = p.row_off[b] + (int64_t)t * (S + 1);
-        const int64_t arow = acts_col_base(p, b, t, rowc);
-        const int lo = p.min_s[c] - 1, hi = min(p.max_s[c], S);
-        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
-        for (int s = wave; s <= S; s += 4) {
-            Sc *__restrict__ g = gs + (arow + s) * (int64_t)V;
-            PathCoef rc{0.0f, 0.0f, 0.0f, 0.0f, kDead};
-            if (s >= lo && s <= hi) rc = path_coef(p, S, s, rowc + s, lab_b);
-            if (rc.lab == kDead) {
-                for (int v = lane; v < V; v += 64) g[v] = zs;
-                continue;
-            }
-            const Sc *__restrict__ z = acts + (arow + s) * (int64_t)V;
-            for (int v = lane; v < V; v += 64) {
-                float gvv = rc.wocc * fast_exp2(fmaf(IO::to_f(z[v]), kLog2e, rc.c2));
-                if (v == blank) gvv -= rc.cb;
-                else if (v == rc.lab) gvv -= rc.ce;
-                g[v] = IO::from_f(gvv);
-            }
-        }
-    }
-}
-
-template <class IO, bool NTL, bool NTS>
-void launch_path_vec(const DevProblem &p, void *grads, int grid, hipStream_t stream) {
-    // 16-byte vectors per lane per chunk and rows per wave as the loss's staged kernel takes them (mrnnt_grad.hip)
-    const int VL = p.V / IO::E;
-    if (VL >= 192) path_grad_staged_kernel<IO, 4, 1, NTL, NTS><<<grid, 256, 0, stream>>>(p, grads);
-    else if (VL >= 96) path_grad_staged_kernel<IO, 2, 2, NTL, NTS><<<grid, 256, 0, stream>>>(p, grads);
-    else path_grad_staged_kernel<IO, 1, 4, NTL, NTS><<<grid, 256, 0, stream>>>(p, grads);
-}
-
-template <class IO>
-void launch_path_io(const DevProblem &p, void *grads, int grid, hipStream_t stream) {
-    const bool vec = (p.V % IO::E) == 0 && (reinterpret_cast<uintptr_t>(p.acts) % 16) == 0 &&
-                     (reinterpret_cast<uintptr_t>(grads) % 16) == 0;
-    if (!vec) {
-        path_grad_scalar_kernel<IO><<<grid, 256, 0, stream>>>(p, grads);
-        return;
-    }
     // few rows are read (at most B K T of them): the loads keep the default policy; the stores are the pass
-    if (tuning().nt_store != 0) launch_path_vec<IO, false, true>(p, grads, grid, stream);
-    else launch_path_vec<IO, false, false>(p, grads, grid, stream);
-}
+    static constexpr bool kNtLoads = false;
+    template <class IO, bool NTL, bool NTS, int U>
+    static void launch_u(const DevProblem &p, const float *, void *grads, int grid, hipStream_t stream) {
+        static_assert(!NTL, "path scores never load nontemporally");
+        grad_staged_kernel<IO, U, staged_rows(U), false, NTS, PathRows><<<grid, 256, 0, stream>>>(p, nullptr, grads);
+    }
+};
 
 // x workgroups of 4 waves per utterance for the (utterance, frame block) kernels
 dim3 block_grid(const DevProblem &p, int T_bound) {
@@ -404,13 +287,7 @@ hipError_t launch_path_coef(const DevProblem &p, const PathArgs &a, int T_bound,
 }
 
 hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream) {
-    switch (elem) {
-        case ELEM_F32: launch_path_io<IoF32>(p, grads, grid, stream); break;
-        case ELEM_BF16: launch_path_io<IoBF16>(p, grads, grid, stream); break;
-        case ELEM_F16: launch_path_io<IoF16>(p, grads, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_grad_rows<PathRows>(p, elem, nullptr, grads, grid, stream);
 }
 
 }  // namespace mrnnt

@@ -362,6 +362,39 @@ RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProb
     return RNNT_STATUS_SUCCESS;
 }
 
+int64_t grad_scatter_above(const Plan &pl) {
+    return ((tuning().col_scatter & 3) != 0 && !(tuning().col_xcd & 3))
+               ? (int64_t)streaming_grid(pl.cols, tuning().grad_grid_per_cu)
+               : INT64_MAX;
+}
+
+RNNTStatus check_row_stride(const char *what, int64_t stride, const char *of, int64_t need, bool dyn, int least) {
+    if (stride >= least && (dyn || stride >= need)) return RNNT_STATUS_SUCCESS;
+    return fail(RNNT_STATUS_INVALID_VALUE, std::string(what) + " row stride " + std::to_string(stride) + " < max " + of +
+                                               " length " + std::to_string(dyn ? (int64_t)least : need));
+}
+
+// device lengths, one workgroup per column wanted: workgroups per CU of the grid that hands the columns out instead
+constexpr int kStealGridPerCU = 16;
+
+RNNTStatus softmax_pass(const Plan &pl, const DevProblem &d, hipStream_t stream) {
+    int grid = streaming_grid(pl.cols, tuning().softmax_grid_per_cu);
+    DevProblem ds = d;  // the log-softmax launch's view
+    ds.col_mul = column_order(pl, 1);
+    if (pl.dyn && tuning().softmax_grid_per_cu <= 0) {  // one workgroup per column needs the column count
+        grid = streaming_grid(pl.cols, kStealGridPerCU);
+        ds.steal = grid < pl.cols;
+    }
+    const hipError_t e = timed(K_SOFTMAX, stream, [&] { return launch_softmax(ds, pl.elem, grid, stream); });
+    return e == hipSuccess ? RNNT_STATUS_SUCCESS : fail_hip(e, "log-softmax kernel");
+}
+
+RNNTStatus posterior_readout(const Plan &pl, const DevProblem &d, const PosteriorArgs &a, hipStream_t stream) {
+    const int grid = streaming_grid((pl.cols + 15) / 16, 8);  // column workgroups: 16 waves, one column per wave
+    const hipError_t e = timed(K_DP, stream, [&] { return launch_posteriors(d, a, grid, stream); });
+    return e == hipSuccess ? RNNT_STATUS_SUCCESS : fail_hip(e, "posterior kernel");
+}
+
 RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws, int num_samples, uint64_t seed,
                           int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
                           hipStream_t stream) {
@@ -374,14 +407,12 @@ RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws
                                                    ") must lie in [0, 2^32]");
     if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
     // with device lengths the kernel bounds every write by the stride instead (and raises the status word)
-    if (out_stride < 1 || (!pl.dyn && out_stride < pl.T_max))
-        return fail(RNNT_STATUS_INVALID_VALUE, "alignments row stride " + std::to_string(out_stride) +
-                                                   " < max input length " + std::to_string(pl.dyn ? 1 : pl.T_max));
+    RNNTStatus st = check_row_stride("alignments", out_stride, "input", pl.T_max, pl.dyn, 1);
+    if (st != RNNT_STATUS_SUCCESS) return st;
     if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
     if (!p->T_dev || !p->S_dev) return fail(RNNT_STATUS_INVALID_VALUE, "device lengths are required");
     if (!p->labels) return fail(RNNT_STATUS_INVALID_VALUE, "labels is null");
     DevProblem d = make_dev(p, pl, ws);  // acts are never read
-    RNNTStatus st;
     if (pl.dyn && (st = status_device_ptr(p, &d.status_host)) != RNNT_STATUS_SUCCESS) return st;
     const SampleArgs a{alignments_dev, out_stride, path_costs_dev, num_samples, first_sample, seed};
     const hipError_t e = timed(K_DP, stream, [&] { return launch_sample(d, a, stream); });

@@ -69,6 +69,13 @@ int64_t column_order(const Plan &pl, int bit);
 // one workgroup per column (hardware-scheduled)
 int streaming_grid(int64_t cols, int per_cu);
 
+// The gradient's DynSetupArgs::scatter_above for the plan: its persistent grid where it walks a scattered order.
+int64_t grad_scatter_above(const Plan &pl);
+
+// A caller's row stride against the longest length it has to hold: "<what> row stride N < max <of> length M". With
+// device lengths only the lower limit `least` (0 or 1) is known on the host (the kernels bound the rest).
+RNNTStatus check_row_stride(const char *what, int64_t stride, const char *of, int64_t need, bool dyn, int least);
+
 // Device address of a caller's status word (host-mapped memory), nullptr for none.
 RNNTStatus status_device_ptr(const mrnnt_problem *p, int **dev);
 int *process_status_word();  // mrnnt_status_word(): one host-mapped word per process
@@ -85,6 +92,13 @@ struct LatticeOpts {
 };
 RNNTStatus prepare_lattice(const mrnnt_problem *p, const Plan &pl, const DevProblem &d, void *ws,
                            const LatticeOpts &o, hipStream_t stream);
+
+// The log-softmax pass over a lattice prepared by prepare_lattice (counted under K_SOFTMAX): one workgroup per column,
+// or with device lengths a work-stealing grid (the column count is not known on the host).
+RNNTStatus softmax_pass(const Plan &pl, const DevProblem &d, hipStream_t stream);
+
+// mrnnt_posteriors / mrnnt_joint_posteriors after their checks: the read-out launch (counted under K_DP).
+RNNTStatus posterior_readout(const Plan &pl, const DevProblem &d, const PosteriorArgs &a, hipStream_t stream);
 
 // mrnnt_sample / mrnnt_joint_sample after their plans: the host checks (before any device call), then the sampler
 // launch on the plan's lattice (counted under K_DP).

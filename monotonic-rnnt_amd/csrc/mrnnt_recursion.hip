@@ -242,16 +242,22 @@ static void launch_halo(const DevProblem &p, int with_beta, float *costs, hipStr
     }
 }
 
-template <int K, int NW>
-static void launch_k(const DevProblem &p, int with_beta, float *costs, hipStream_t stream) {
-    // D = rows of lp prefetched ahead (register ring), shallower where K cells per lane use the registers
-    constexpr int D = K <= 2 ? 8 : (K <= 4 ? 4 : (K <= 8 ? 2 : 1));
-    const int blocks = with_beta ? 2 * p.B : p.B;
-    if (p.min_s)
-        recursion_kernel<K, D, NW, true><<<blocks, 64 * NW, 0, stream>>>(p, with_beta, costs);
-    else
-        recursion_kernel<K, D, NW, false><<<blocks, 64 * NW, 0, stream>>>(p, with_beta, costs);
-}
+struct DpLaunch {  // launch_by_width's go<K, NW>() for recursion_kernel
+    const DevProblem &p;
+    int with_beta;
+    float *costs;
+    hipStream_t stream;
+    template <int K, int NW>
+    void go() const {
+        // D = rows of lp prefetched ahead (register ring), shallower where K cells per lane use the registers
+        constexpr int D = K <= 2 ? 8 : (K <= 4 ? 4 : (K <= 8 ? 2 : 1));
+        const int blocks = with_beta ? 2 * p.B : p.B;
+        if (p.min_s)
+            recursion_kernel<K, D, NW, true><<<blocks, 64 * NW, 0, stream>>>(p, with_beta, costs);
+        else
+            recursion_kernel<K, D, NW, false><<<blocks, 64 * NW, 0, stream>>>(p, with_beta, costs);
+    }
+};
 
 // NW waves x K cells per lane, sized to the longest S+1 of the batch: the per-step latency is one fp64
 // LSE chain of K cells plus (NW > 1) one barrier, so small S runs on one wave with no barrier at all.
@@ -273,17 +279,8 @@ hipError_t launch_dp(const DevProblem &p, int S_max, int with_beta, float *costs
         }
         return hipGetLastError();
     }
-    if constexpr (kVariants) {  // dp_halo = 0 (development build): the per-step-barrier kernel for short rows too
-        if (W <= 64) launch_k<1, 1>(p, with_beta, costs, stream);
-        else if (W <= 128) launch_k<1, 2>(p, with_beta, costs, stream);
-        else if (W <= 256) launch_k<1, 4>(p, with_beta, costs, stream);
-        if (W <= 256) return hipGetLastError();
-    }
-    if (W <= 512) launch_k<1, 8>(p, with_beta, costs, stream);
-    else if (W <= 1024) launch_k<2, 8>(p, with_beta, costs, stream);
-    else if (W <= 1536) launch_k<3, 8>(p, with_beta, costs, stream);
-    else if (W <= kMaxLabelsPlusOne) launch_k<4, 8>(p, with_beta, costs, stream);
-    else return hipErrorInvalidValue;
+    // (the short shapes: dp_halo = 0, development build -- the per-step-barrier kernel for short rows too)
+    if (!launch_by_width<kVariants>(W, DpLaunch{p, with_beta, costs, stream})) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -172,28 +172,26 @@ __global__ __launch_bounds__(64 * NW) void viterbi_kernel(DevProblem p, int *__r
     backtrace<K, NW>(p, b, fin, out, out_stride, costs, bt);
 }
 
-template <int K, int NW>
-static void launch_vk(const DevProblem &p, int *out, int64_t out_stride, float *costs, hipStream_t stream) {
-    constexpr int D = K <= 2 ? 8 : 4;  // lp rows prefetched ahead, as launch_k (mrnnt_recursion.hip)
-    if (p.min_s)
-        viterbi_kernel<K, D, NW, true><<<p.B, 64 * NW, 0, stream>>>(p, out, out_stride, costs);
-    else
-        viterbi_kernel<K, D, NW, false><<<p.B, 64 * NW, 0, stream>>>(p, out, out_stride, costs);
-}
+struct ViterbiLaunch {  // launch_by_width's go<K, NW>() for viterbi_kernel
+    const DevProblem &p;
+    int *out;
+    int64_t out_stride;
+    float *costs;
+    hipStream_t stream;
+    template <int K, int NW>
+    void go() const {
+        constexpr int D = K <= 2 ? 8 : 4;  // lp rows prefetched ahead, as DpLaunch (mrnnt_recursion.hip)
+        if (p.min_s)
+            viterbi_kernel<K, D, NW, true><<<p.B, 64 * NW, 0, stream>>>(p, out, out_stride, costs);
+        else
+            viterbi_kernel<K, D, NW, false><<<p.B, 64 * NW, 0, stream>>>(p, out, out_stride, costs);
+    }
+};
 
-// NW waves x K cells per lane from the longest S+1 of the batch, as launch_k: one wave (no barrier in the step) up
-// to 64 cells, then one cell per lane on 2 / 4 / 8 waves, then 2 / 3 / 4 cells per lane on 8 waves.
+// one wave (no barrier in the step) up to 64 cells, then as the recursion (launch_by_width, mrnnt_dp.h)
 hipError_t launch_viterbi(const DevProblem &p, int S_max, int *out, int64_t out_stride, float *costs,
                           hipStream_t stream) {
-    const int W = S_max + 1;
-    if (W <= 64) launch_vk<1, 1>(p, out, out_stride, costs, stream);
-    else if (W <= 128) launch_vk<1, 2>(p, out, out_stride, costs, stream);
-    else if (W <= 256) launch_vk<1, 4>(p, out, out_stride, costs, stream);
-    else if (W <= 512) launch_vk<1, 8>(p, out, out_stride, costs, stream);
-    else if (W <= 1024) launch_vk<2, 8>(p, out, out_stride, costs, stream);
-    else if (W <= 1536) launch_vk<3, 8>(p, out, out_stride, costs, stream);
-    else if (W <= kMaxLabelsPlusOne) launch_vk<4, 8>(p, out, out_stride, costs, stream);
-    else return hipErrorInvalidValue;
+    if (!launch_by_width<true>(S_max + 1, ViterbiLaunch{p, out, out_stride, costs, stream})) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -326,22 +326,28 @@ def _on_device(dev: torch.device):
     return _NULL_CTX if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
 
 
-def _forward(prep: _Prepared, with_beta: bool):
+def _call(prep: _Prepared, name: str, *args, pending: bool = False, lengths: bool = True):
+    """Runs entry point `name` where the inputs live: mrnnt_cpu_<name>(problem, *args, num_threads) on the host, else
+    mrnnt_<name>(problem, *args, stream) on the device's current stream. GPU-resident lengths: `pending` first surfaces
+    an earlier call's failed validation (no wait); `lengths` is the MRNNT_SYNC_LENGTH_CHECK tail."""
     lib = _L.load()
-    ws = prep.workspace()
-    costs = torch.empty(prep.problem.B, dtype=torch.float32, device=prep.device)
     if not prep.on_gpu:
-        _L.check(lib.mrnnt_cpu_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(costs),
-                                       1 if with_beta else 0, prep.num_threads), "mrnnt_cpu_forward")
-        return costs, ws
-    if prep.dyn:
-        check_lengths(sync=False)  # an earlier call's failed validation surfaces here (no wait)
+        _L.check(getattr(lib, "mrnnt_cpu_" + name)(ctypes.byref(prep.problem), *args, prep.num_threads),
+                 "mrnnt_cpu_" + name)
+        return
+    if pending and prep.dyn:
+        check_lengths(sync=False)
     with _on_device(prep.device):  # kernels go to this device's current stream
-        _L.check(lib.mrnnt_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(costs),
-                                   1 if with_beta else 0, prep.stream()), "mrnnt_forward")
-        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
+        _L.check(getattr(lib, "mrnnt_" + name)(ctypes.byref(prep.problem), *args, prep.stream()), "mrnnt_" + name)
+        if lengths and prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(prep.device).synchronize()
             check_lengths(sync=False)
+
+
+def _forward(prep: _Prepared, with_beta: bool):
+    ws = prep.workspace()
+    costs = torch.empty(prep.problem.B, dtype=torch.float32, device=prep.device)
+    _call(prep, "forward", _ptr(ws), ws.numel(), _ptr(costs), 1 if with_beta else 0, pending=True)
     return costs, ws
 
 
@@ -359,13 +365,7 @@ def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tens
             prep.problem.grad_scale_broadcast = 1
         else:
             grad_scale = grad_scale.to(prep.device, torch.float32).contiguous()
-    if not prep.on_gpu:
-        _L.check(_L.load().mrnnt_cpu_backward(ctypes.byref(prep.problem), _ptr(ws), _ptr(grad_scale), _ptr(grads),
-                                              prep.num_threads), "mrnnt_cpu_backward")
-        return grads
-    with _on_device(prep.device):
-        _L.check(_L.load().mrnnt_backward(ctypes.byref(prep.problem), _ptr(ws), _ptr(grad_scale), _ptr(grads),
-                                          prep.stream()), "mrnnt_backward")
+    _call(prep, "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
     return grads
 
 
@@ -421,6 +421,25 @@ def monotonic_rnnt_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths:
     return result
 
 
+def _readout_length(prep, max_input_length, who):
+    """Row length of a per-frame read-out: max_input_length, else the padded acts' frames, else the longest host length,
+    else the alignment's row length."""
+    if max_input_length is not None:
+        L = int(max_input_length)
+    elif prep.acts.dim() == 4:
+        L = prep.acts.size(1)
+    elif not prep.dyn:
+        L = int(prep.T_host.max())
+    elif prep.alignment is not None:
+        L = prep.alignment.size(1)
+    else:
+        raise RuntimeError(f"{who}: with GPU-resident lengths and packed acts the longest input length "
+                           "is not known on the host; pass max_input_length (>= every input length)")
+    if L < 1:
+        raise RuntimeError(f"{who}: max_input_length must be >= 1, got {L}")
+    return L
+
+
 def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                          label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
                          max_distance_from_alignment: int = 0, blank_label: int = 0,
@@ -441,36 +460,12 @@ def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths
     GPU-resident lengths that fail validation surface through check_lengths() exactly as for the loss."""
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
-    if max_input_length is not None:
-        L = int(max_input_length)
-    elif prep.acts.dim() == 4:
-        L = prep.acts.size(1)
-    elif not prep.dyn:
-        L = int(prep.T_host.max())
-    elif prep.alignment is not None:
-        L = prep.alignment.size(1)
-    else:
-        raise RuntimeError("monotonic_rnnt_align: with GPU-resident lengths and packed acts the longest input length "
-                           "is not known on the host; pass max_input_length (>= every input length)")
-    if L < 1:
-        raise RuntimeError(f"monotonic_rnnt_align: max_input_length must be >= 1, got {L}")
-    lib = _L.load()
+    L = _readout_length(prep, max_input_length, "monotonic_rnnt_align")
     ws = prep.workspace()
     B = prep.problem.B
     out = torch.empty((B, L), dtype=torch.int32, device=prep.device)
     costs = torch.empty(B, dtype=torch.float32, device=prep.device)
-    if not prep.on_gpu:
-        _L.check(lib.mrnnt_cpu_align(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs),
-                                     prep.num_threads), "mrnnt_cpu_align")
-        return out, costs
-    if prep.dyn:
-        check_lengths(sync=False)  # an earlier call's failed validation surfaces here (no wait)
-    with _on_device(prep.device):
-        _L.check(lib.mrnnt_align(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs),
-                                 prep.stream()), "mrnnt_align")
-        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(prep.device).synchronize()
-            check_lengths(sync=False)
+    _call(prep, "align", _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs), pending=True)
     return out, costs
 
 
@@ -502,19 +497,7 @@ def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_le
     validation make every value NaN and surface through check_lengths() exactly as for the loss."""
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
-    if max_input_length is not None:
-        L = int(max_input_length)
-    elif prep.acts.dim() == 4:
-        L = prep.acts.size(1)
-    elif not prep.dyn:
-        L = int(prep.T_host.max())
-    elif prep.alignment is not None:
-        L = prep.alignment.size(1)
-    else:
-        raise RuntimeError("monotonic_rnnt_posteriors: with GPU-resident lengths and packed acts the longest input "
-                           "length is not known on the host; pass max_input_length (>= every input length)")
-    if L < 1:
-        raise RuntimeError(f"monotonic_rnnt_posteriors: max_input_length must be >= 1, got {L}")
+    L = _readout_length(prep, max_input_length, "monotonic_rnnt_posteriors")
     costs, ws = _forward(prep, with_beta=True)
     B, dev = prep.problem.B, prep.device
     Sw = labels.size(1) if labels.dim() == 2 else prep.labels.size(1)
@@ -522,17 +505,7 @@ def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_le
     label = torch.empty_like(blank)
     emit = torch.empty((B, L), dtype=torch.float32, device=dev)
     label_time = torch.empty((B, Sw), dtype=torch.float32, device=dev)
-    lib = _L.load()
-    if not prep.on_gpu:
-        _L.check(lib.mrnnt_cpu_posteriors(ctypes.byref(prep.problem), _ptr(ws), _ptr(blank), _ptr(label), _ptr(emit), L,
-                                          _ptr(label_time), Sw, prep.num_threads), "mrnnt_cpu_posteriors")
-        return Posteriors(blank, label, emit, label_time, costs)
-    with _on_device(dev):
-        _L.check(lib.mrnnt_posteriors(ctypes.byref(prep.problem), _ptr(ws), _ptr(blank), _ptr(label), _ptr(emit), L,
-                                      _ptr(label_time), Sw, prep.stream()), "mrnnt_posteriors")
-        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(dev).synchronize()
-            check_lengths(sync=False)
+    _call(prep, "posteriors", _ptr(ws), _ptr(blank), _ptr(label), _ptr(emit), L, _ptr(label_time), Sw)
     return Posteriors(blank, label, emit, label_time, costs)
 
 
@@ -573,36 +546,14 @@ def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_length
     K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_sample")
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
-    if max_input_length is not None:
-        L = int(max_input_length)
-    elif prep.acts.dim() == 4:
-        L = prep.acts.size(1)
-    elif not prep.dyn:
-        L = int(prep.T_host.max())
-    elif prep.alignment is not None:
-        L = prep.alignment.size(1)
-    else:
-        raise RuntimeError("monotonic_rnnt_sample: with GPU-resident lengths and packed acts the longest input "
-                           "length is not known on the host; pass max_input_length (>= every input length)")
-    if L < 1:
-        raise RuntimeError(f"monotonic_rnnt_sample: max_input_length must be >= 1, got {L}")
+    L = _readout_length(prep, max_input_length, "monotonic_rnnt_sample")
     if K < 1:
         raise RuntimeError(f"monotonic_rnnt_sample: num_samples must be >= 1, got {K}")
     costs, ws = _forward(prep, with_beta=True)
     B, dev = prep.problem.B, prep.device
     out = torch.empty((B, K, L), dtype=torch.int32, device=dev)
     path_costs = torch.empty((B, K), dtype=torch.float32, device=dev)
-    lib = _L.load()
-    if not prep.on_gpu:
-        _L.check(lib.mrnnt_cpu_sample(ctypes.byref(prep.problem), _ptr(ws), K, seed, first, _ptr(out), L,
-                                      _ptr(path_costs), prep.num_threads), "mrnnt_cpu_sample")
-        return Samples(out, path_costs, costs)
-    with _on_device(dev):
-        _L.check(lib.mrnnt_sample(ctypes.byref(prep.problem), _ptr(ws), K, seed, first, _ptr(out), L,
-                                  _ptr(path_costs), prep.stream()), "mrnnt_sample")
-        if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(dev).synchronize()
-            check_lengths(sync=False)
+    _call(prep, "sample", _ptr(ws), K, seed, first, _ptr(out), L, _ptr(path_costs))
     return Samples(out, path_costs, costs)
 
 
@@ -625,21 +576,9 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
         K, L = al.size(1), al.size(2)
         if K < 1 or L < 1:
             raise RuntimeError(f"monotonic_rnnt_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got {K}, {L}")
-        lib = _L.load()
         ws = prep.workspace(num_paths=K)
         costs = torch.empty((B, K), dtype=torch.float32, device=dev)
-        if not prep.on_gpu:
-            _L.check(lib.mrnnt_cpu_path_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
-                                                _ptr(costs), prep.num_threads), "mrnnt_cpu_path_forward")
-        else:
-            if prep.dyn:
-                check_lengths(sync=False)  # an earlier call's failed validation surfaces here (no wait)
-            with _on_device(dev):
-                _L.check(lib.mrnnt_path_forward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
-                                                _ptr(costs), prep.stream()), "mrnnt_path_forward")
-                if prep.dyn and _SYNC_LENGTH_CHECK and not torch.cuda.is_current_stream_capturing():
-                    torch.cuda.current_stream(dev).synchronize()
-                    check_lengths(sync=False)
+        _call(prep, "path_forward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(costs), pending=True)
         if ctx.needs_input_grad[0]:
             # acts is re-read by the gradient kernel on the rows the paths visit; the workspace holds den, the hull
             # and the paths' validity
@@ -655,14 +594,7 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
         w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
         # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), as the loss's
         grads = _GP.grads_like(prep.acts) if prep.on_gpu else torch.empty_like(prep.acts)
-        lib = _L.load()
-        if not prep.on_gpu:
-            _L.check(lib.mrnnt_cpu_path_backward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
-                                                 _ptr(w), _ptr(grads), prep.num_threads), "mrnnt_cpu_path_backward")
-        else:
-            with _on_device(prep.device):
-                _L.check(lib.mrnnt_path_backward(ctypes.byref(prep.problem), _ptr(ws), ws.numel(), _ptr(al), K, L,
-                                                 _ptr(w), _ptr(grads), prep.stream()), "mrnnt_path_backward")
+        _call(prep, "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads), lengths=False)
         return grads, None, None, None, None, None
 
 
