@@ -463,6 +463,56 @@ RNNTStatus mrnnt_joint_reduce_pre(const mrnnt_joint_problem *p, void *workspace,
 /* (version 9) Bytes of p->reduce_scratch for the blocked form of mrnnt_joint_reduce. */
 RNNTStatus mrnnt_joint_reduce_scratch_bytes(const mrnnt_joint_problem *p, size_t *bytes);
 
+/* mrnnt_path_forward / mrnnt_path_backward for the fused joint (an addition to version 13: MRNNT_VERSION and both
+ * structs are unchanged, so callers that may meet an older build of version 13 probe for the symbol
+ * mrnnt_joint_path_forward): differentiable scores of num_paths GIVEN alignments per utterance under the logits the
+ * joint never stores, and the gradients of sum_{b,k} w[b, k] * path_costs[b, k] for enc, pred, weight and bias through
+ * the joint's own backward chain over the rows the paths stand on -- at most num_paths * T_b per utterance -- with no
+ * dense logit gradient at all. The contract of mrnnt_path_*, stated once more for the joint:
+ *   alignments_dev[(b*num_paths + k)*path_stride + t], t < T_b: p->blank or the label frame t emits (the format
+ *       mrnnt_joint_align / mrnnt_joint_sample write); entries at t >= T_b are not read.
+ *   Row (b, k) is walked from s = 0: p->blank takes the blank arc of row (t, s); labels[b, s] with s < S_b takes the
+ *       label arc, then s += 1; anything else (a wrong or negative value, the -1 sentinel rows, a label at s = S_b), or
+ *       s != S_b after frame T_b - 1, makes the row INVALID: it costs +inf and contributes nothing whatever its weight.
+ *   path_costs_dev[b*num_paths + k] (may be NULL) = fp32(-sum_t lp(arc_t)), lp the pairs mrnnt_joint_forward leaves in
+ *       the workspace (the same kernel on the same operands; an out-of-range device label: NaN), summed in fp64 in the
+ *       fixed order of mrnnt_path_forward. Only the rows between the lowest and the highest valid path of each frame
+ *       (the hull) are computed, plus row (0, 0) of an utterance without a valid path. No recursion runs.
+ *   With Wb(r) / We(r) the fp64 sums, in ascending k, of the weights of the VALID paths that leave row r by its blank /
+ *       label arc, the logit gradient of row r is mrnnt_path_backward's,
+ *           g[r, v] = (Wb + We) softmax(z_r)[v] - [v == blank] Wb - [v == label(s)] We.
+ *       A row with Wb == 0 && We == 0 is not in the backward's row list; Wb == -We != 0 is a live row whose softmax
+ *       term cancels and whose two corrections stay.
+ *   Costs and all four gradients are bitwise reproducible.
+ * Calls, on one workspace of mrnnt_joint_path_workspace_size(p, num_paths) bytes:
+ *   mrnnt_joint_path_forward: walk + hull, the list of the hull rows (its count stays on the device), the joint
+ *       log-softmax pass over that list, the score launch.
+ *   mrnnt_joint_path_rows (after it, same alignments): weights_dev[b*num_paths + k] (fp32, signed; NULL = 1) is the
+ *       upstream gradient of path_costs; the coefficient launch, then the list of the path-live rows (inside the hull,
+ *       Wb != 0 || We != 0) with its count in *count_dev (device uint64). mrnnt_joint_path_row_bound is a host-known
+ *       upper bound on that count: sum_b min(num_paths * T_b, in-band rows of b).
+ *   mrnnt_joint_path_backward: mrnnt_joint_backward over that list with the path coefficients in place of the loss's
+ *       (no grad_scale: the weights are in Wb / We). G, Hact, bt_idx, bs_idx, p->hact_ld, p->dbias and
+ *       p->live_count_dev (n_rows then a host bound, rows [count, n_rows) zeroed) as there.
+ *   Then mrnnt_joint_dpre / mrnnt_joint_reduce / mrnnt_joint_reduce_pre exactly as after mrnnt_joint_backward: the
+ *       workspace is laid out as mrnnt_joint_workspace_size's of the same problem FOLLOWED by the hull arrays and a few
+ *       words per path, so those entry points work on it unchanged (the reduce takes its column offsets from the last
+ *       list built, the path-live one).
+ * Checked on the host before any device call, workspace included (RNNT_STATUS_INVALID_VALUE): p->alignment == NULL
+ * (the band arrays hold the hull); num_paths >= 1; alignments_dev != NULL; path_stride >= max T_b; everything
+ * mrnnt_joint_workspace_size checks. Asynchronous on `stream`, no host read. The walk, score and coefficient launches
+ * count under [2] of mrnnt_profile_read, the joint pass under [5], the gradient pass under [6]. */
+RNNTStatus mrnnt_joint_path_workspace_size(const mrnnt_joint_problem *p, int num_paths, size_t *bytes);
+RNNTStatus mrnnt_joint_path_row_bound(const mrnnt_joint_problem *p, int num_paths, int64_t *rows);
+RNNTStatus mrnnt_joint_path_forward(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                    const int *alignments_dev, int num_paths, int64_t path_stride,
+                                    float *path_costs_dev, hipStream_t stream);
+RNNTStatus mrnnt_joint_path_rows(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                 const int *alignments_dev, int num_paths, int64_t path_stride,
+                                 const float *weights_dev, unsigned long long *count_dev, hipStream_t stream);
+RNNTStatus mrnnt_joint_path_backward(const mrnnt_joint_problem *p, void *workspace, int64_t n_rows, void *G, void *Hact,
+                                     int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream);
+
 /* Nontemporal zero fill of `bytes` (a multiple of 16) at `dst` (16-byte aligned device memory), in the gradient
  * pass's store pattern. The Python surface times it once over a newly allocated large grads buffer to pick a
  * fast-writing physical placement; also usable as a plain fill. Asynchronous on `stream`. */

@@ -240,24 +240,9 @@ RNNTStatus make_path_plan(const mrnnt_problem *p, int num_paths, PathPlan *pp) {
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride) {
-    if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
-    // with device lengths T_b <= path_stride joins the device validation
-    return check_row_stride("alignments", path_stride, "input", pl.T_max, pl.dyn, 1);
-}
-
 PathArgs path_args(const PathPlan &pp, void *ws, const int *alignments_dev, int num_paths, int64_t path_stride) {
-    PathArgs a;
-    a.al = alignments_dev;
-    a.stride = path_stride;
-    a.K = num_paths;
-    a.valid = carve<int>(ws, pp.off_valid);
-    a.carry = carve<int>(ws, pp.off_carry);
-    a.min_s = carve<int>(ws, pp.pl.off_min);
-    a.max_s = carve<int>(ws, pp.pl.off_max);
-    a.costs = nullptr;
-    a.w = nullptr;
-    return a;
+    return mrnnt::path_args(ws, pp.off_valid, pp.off_carry, pp.pl.off_min, pp.pl.off_max, alignments_dev, num_paths,
+                            path_stride);
 }
 
 }  // namespace

@@ -106,13 +106,17 @@ struct JointArgs {
                                  // timeline stamps (g_reduce_trace)
 };
 
-// Row lists over the lattice: mode 0 = every in-band row, mode 1 = live rows (needs alpha/beta/ll).
+// Row lists over the lattice: mode 0 = every in-band row, mode 1 = live rows (needs alpha/beta/ll), mode 2 =
+// path-live rows (mrnnt_joint_path_*: the rows of the column's hull, p.min_s / p.max_s, whose path weights Wb / We in
+// p.alpha / p.beta are not both zero; nothing outside the hull is read).
 hipError_t launch_row_list(const DevProblem &p, int mode, int64_t *col_cnt, int *lcol, int *ls,
                            unsigned long long *total, hipStream_t stream);
 hipError_t launch_joint_forward(const DevProblem &p, const JointArgs &j, hipStream_t stream);
 // flag = 1 when max_v (sum_h |W[v, h]| + |bias[v]|) <= 64 (then |z| <= 64 for every logit: |tanh| <= 1), else 0
 hipError_t launch_joint_wbound(const unsigned short *W, const float *bias, int V, int H, int *flag, hipStream_t stream);
-hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream);
+// path_coef: the rows' coefficients are the path weights Wb / We (p.alpha / p.beta after launch_path_coef) and den,
+// g = (Wb + We) softmax - [blank] Wb - [label] We; j.scale is not read
+hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream, bool path_coef = false);
 hipError_t launch_joint_reduce(const DevProblem &p, const JointArgs &j, const int64_t *off, int T_max, int S_max,
                                const unsigned short *dH, float *d_enc, float *d_pred, void *scratch,
                                size_t scratch_bytes, hipStream_t stream);

@@ -79,10 +79,13 @@ __device__ __forceinline__ f2 fast_tanh2(f2 x) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// row lists: entries (column, s) in column order, s ascending; mode 0 = in-band rows, 1 = live rows
+// row lists: entries (column, s) in column order, s ascending; mode 0 = in-band rows, 1 = live rows, 2 = path-live
+// rows (mrnnt_joint_path_rows): the rows of the column's hull whose path weights Wb / We (p.alpha / p.beta after
+// launch_path_coef) are not both zero
 
 __device__ __forceinline__ bool list_pred(const DevProblem &p, int mode, int t, int s, int64_t row, int W,
                                           double ll) {
+    if (mode == 2) return p.alpha[row] != 0.0 || p.beta[row] != 0.0;
     if (mode == 0 || !p.occ_skip) return true;
     return row_live(alpha_prev(p, t, s, row, W) - ll + p.beta[row]);
 }
@@ -96,7 +99,13 @@ __device__ __forceinline__ void row_list_column(const DevProblem &p, int mode, i
     const int64_t rowc = p.row_off[b] + (int64_t)t * W;
     int lo = max(0, t - (T - S)), hi = min(t, S);
     if (mode == 0) align_window(p, col, t, lo, hi);  // alignment-restricted: only the rows the recursion uses
-    const double ll = mode ? p.ll[b] : 0.0;
+    if (mode == 2) {
+        // the hull rows as path_coef_kernel zeroed them and PathRows::column reads them (not align_window): Wb / We
+        // outside are uninitialised and never looked at; a column without a valid path holds {kHullEmpty, -1}: no rows
+        lo = max(lo, p.min_s[col] - 1);
+        hi = min(hi, p.max_s[col]);
+    }
+    const double ll = mode == 1 ? p.ll[b] : 0.0;
     int64_t base = WRITE ? cnt[col] : 0;
     int n = 0;
     for (int s0 = lo; s0 <= hi; s0 += 64) {
@@ -202,7 +211,7 @@ struct RowPos {
 };
 
 __device__ __forceinline__ int64_t list_len(const JointArgs &j) {
-    return j.n_dev ? (int64_t)*j.n_dev : j.n;
+    return j.n_dev ? min((int64_t)*j.n_dev, j.n) : j.n;  // (a device count never reaches past the host bound)
 }
 
 __device__ __forceinline__ RowPos row_pos(const DevProblem &p, const JointArgs &j, int64_t i) {
@@ -659,7 +668,57 @@ int joint_trace(unsigned long long *out, int n) {
 }
 #endif
 
-template <int KS, int NB, int NW, int RG>
+// Row coefficients of the MFMA gradient kernels (the policy mrnnt_grad.h gives the streaming kernels): what a list row
+// stages once, and what the chunk epilogue makes of e = exp2(z log2 e + c2) -- a plain entry, the row's blank / label
+// entry, and the two corrections' share of the dbias column sums.
+// The loss: g = scale * (softmax occupancy - corrections), coefficients from alpha / beta / ll (row_coef).
+struct LossCoef {
+    float c2, cb, ce, sc;
+    int lab;
+    __device__ __forceinline__ void clear() {
+        c2 = cb = ce = sc = 0.0f;
+        lab = -1;
+    }
+    __device__ __forceinline__ void stage(const DevProblem &p, const JointArgs &j, const RowPos &q) {
+        const RowCoef rc =
+            row_coef(p, q.t, q.T, q.S, q.s, q.row, p.ll[q.b], p.labels + (int64_t)q.b * p.label_stride);
+        c2 = rc.c2, cb = rc.cb, ce = rc.ce, lab = rc.lab;
+        sc = j.scale ? j.scale[q.b] : 1.0f;
+    }
+    __device__ __forceinline__ float out(float e) const { return e * sc; }
+    __device__ __forceinline__ float out_blank(float e) const { return (e - cb) * sc; }
+    __device__ __forceinline__ float out_label(float e) const { return (e - ce) * sc; }
+    __device__ __forceinline__ float sum_blank() const { return cb * sc; }
+    __device__ __forceinline__ float sum_label() const { return ce * sc; }
+};
+
+// Path scores (mrnnt_joint_path_backward): g = wocc * softmax - [blank] Wb - [label] We, the formula of PathRows::grad
+// (mrnnt_path.hip), with Wb / We in p.alpha / p.beta (launch_path_coef) and den from the forward. wocc = Wb + We is a
+// signed multiplier -- never a divisor: wocc = 0 with Wb = -We != 0 is a live row whose two corrections stay. Only
+// listed rows are staged (path-live: inside the hull), so nothing uninitialised is read.
+struct PathCoef {
+    float c2, wocc, cb, ce;
+    int lab;
+    __device__ __forceinline__ void clear() {
+        c2 = wocc = cb = ce = 0.0f;
+        lab = -1;
+    }
+    __device__ __forceinline__ void stage(const DevProblem &p, const JointArgs &, const RowPos &q) {
+        const double wb = p.alpha[q.row], we = p.beta[q.row];
+        c2 = p.den[q.row] * kLog2e;
+        wocc = (float)(wb + we);
+        cb = (float)wb;
+        ce = (float)we;
+        lab = (q.lab < 0 || q.lab == p.blank) ? -1 : q.lab;  // (s == S, out of range, label == blank: as row_coef)
+    }
+    __device__ __forceinline__ float out(float e) const { return wocc * e; }
+    __device__ __forceinline__ float out_blank(float e) const { return wocc * e - cb; }
+    __device__ __forceinline__ float out_label(float e) const { return wocc * e - ce; }
+    __device__ __forceinline__ float sum_blank() const { return cb; }
+    __device__ __forceinline__ float sum_label() const { return ce; }
+};
+
+template <int KS, int NB, int NW, int RG, class RC>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void joint_bwd_kernel(DevProblem p,
                                                                                              JointArgs j) {
     extern __shared__ __attribute__((aligned(16))) unsigned short wsh[];
@@ -667,11 +726,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int lane = threadIdx.x & 63, half = lane >> 5;
     const int64_t i = (int64_t)blockIdx.x * (32 * NW) + (threadIdx.x >> 6) * 32 + (lane & 31);
     const RowPos q = row_pos(p, j, i);
-    RowCoef rc{0.0f, 0.0f, 0.0f, -1, false};
-    float sc = 0.0f;
+    RC rc;
+    rc.clear();
     if (q.valid) {
-        rc = row_coef(p, q.t, q.T, q.S, q.s, q.row, p.ll[q.b], p.labels + (int64_t)q.b * p.label_stride);
-        sc = j.scale ? j.scale[q.b] : 1.0f;
+        rc.stage(p, j, q);
         if (half == 0 && j.bt_idx) j.bt_idx[i] = (int64_t)q.b * (j.enc_sb / j.H) + q.t;
         if (half == 0 && j.bs_idx) j.bs_idx[i] = (int64_t)q.b * (j.pred_sb / j.H) + q.s;
     }
@@ -685,7 +743,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const bool vec_out = (V & 3) == 0;
     const bool leave = vec_out && __ballot(!q.valid) == 0;
     unsigned short *grow = j.G + (q.valid ? i : 0) * V;
-    const f2 l2e = {kLog2e, kLog2e}, c2 = {rc.c2, rc.c2}, sc2 = {sc, sc};
+    const f2 l2e = {kLog2e, kLog2e}, c2 = {rc.c2, rc.c2};
     chunk_loop<KS, NB, NW, RG>(j, V, wsh, bfr, lane, leave ? 4 : -1, [&](const f32x16 &acc, int c) {
         f2 g[8];
         logits2(acc, bias, c, half, g);
@@ -704,7 +762,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (rb >= 0) gb = tree_pick(g, rb);
         if (__ballot(mine)) gl = tree_pick(g, rl);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) g[k] = mul2(g[k], sc2);
+        for (int k = 0; k < 8; ++k) g[k] = (f2){rc.out(g[k].x), rc.out(g[k].y)};
         if (q.valid) {
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
@@ -720,8 +778,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                         if (v0 + e < V) grow[v0 + e] = IoBF16::from_f(e4[e]);
                 }
             }
-            if (rb >= 0) grow[blank] = IoBF16::from_f((gb - rc.cb) * sc);
-            if (mine) grow[rc.lab] = IoBF16::from_f((gl - rc.ce) * sc);
+            if (rb >= 0) grow[blank] = IoBF16::from_f(rc.out_blank(gb));
+            if (mine) grow[rc.lab] = IoBF16::from_f(rc.out_label(gl));
         }
     });
 }
@@ -751,7 +809,7 @@ __device__ __forceinline__ void logits8(const typename WTile16<KS>::Acc &acc, co
         for (int r = 0; r < 4; ++r) x[4 * vt + r] = acc.d[vt][rt][r] + bv[vt][r];
 }
 
-template <int KS, int NB, int NW>
+template <int KS, int NB, int NW, class RC>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void joint_bwd16_kernel(
     DevProblem p, JointArgs j) {
     extern __shared__ __attribute__((aligned(16))) unsigned short wsh[];
@@ -765,17 +823,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int lane = threadIdx.x & 63, c16 = lane & 15, g = lane >> 4;
     const int64_t i0 = (int64_t)blockIdx.x * (32 * NW) + (threadIdx.x >> 6) * 32 + c16;
     const RowPos q[2] = {row_pos(p, j, i0), row_pos(p, j, i0 + 16)};
-    RowCoef rc[2];
-    float sc[2];
+    RC rc[2];
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
         const RowPos &qr = q[rt];
         const int64_t i = i0 + 16 * rt;
-        rc[rt] = RowCoef{0.0f, 0.0f, 0.0f, -1, false};
-        sc[rt] = 0.0f;
+        rc[rt].clear();
         if (qr.valid) {
-            rc[rt] = row_coef(p, qr.t, qr.T, qr.S, qr.s, qr.row, p.ll[qr.b], p.labels + (int64_t)qr.b * p.label_stride);
-            sc[rt] = j.scale ? j.scale[qr.b] : 1.0f;
+            rc[rt].stage(p, j, qr);
             if (g == 0 && j.bt_idx) j.bt_idx[i] = (int64_t)qr.b * (j.enc_sb / j.H) + qr.t;
             if (g == 0 && j.bs_idx) j.bs_idx[i] = (int64_t)qr.b * (j.pred_sb / j.H) + qr.s;
         }
@@ -820,11 +875,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if (jb >= 0 && jb < 32) gb = pick8(x, pick8_index(jb));
                 if (__ballot(mine)) gl = pick8(x, pick8_index(jl & 31));
                 if (q[rt].valid) {
-                    const float s = sc[rt];
 #pragma unroll
                     for (int vt = 0; vt < 2; ++vt) {
                         const int v0 = 32 * c + 16 * vt + 4 * g;
-                        const float e4[4] = {x[4 * vt] * s, x[4 * vt + 1] * s, x[4 * vt + 2] * s, x[4 * vt + 3] * s};
+                        const float e4[4] = {rc[rt].out(x[4 * vt]), rc[rt].out(x[4 * vt + 1]), rc[rt].out(x[4 * vt + 2]),
+                                             rc[rt].out(x[4 * vt + 3])};
 #pragma unroll
                         for (int e = 0; e < 4; ++e) cs[4 * vt + e] += e4[e];
                         if (vec_out && v0 + 3 < V) {
@@ -836,11 +891,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                                 if (v0 + e < V) grow[rt][v0 + e] = IoBF16::from_f(e4[e]);
                         }
                     }
-                    if (hb) grow[rt][blank] = IoBF16::from_f((gb - rc[rt].cb) * s);
-                    if (mine) grow[rt][rc[rt].lab] = IoBF16::from_f((gl - rc[rt].ce) * s);
+                    if (hb) grow[rt][blank] = IoBF16::from_f(rc[rt].out_blank(gb));
+                    if (mine) grow[rt][rc[rt].lab] = IoBF16::from_f(rc[rt].out_label(gl));
                     if (j.dbias) {  // the two corrected entries: the column sums above hold them uncorrected
                         const int kb = hb ? pick8_index(jb) : -1, kl = mine ? pick8_index(jl & 31) : -1;
-                        const float db = rc[rt].cb * s, dl = rc[rt].ce * s;
+                        const float db = rc[rt].sum_blank(), dl = rc[rt].sum_label();
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
                             if (k == kb) cs[k] -= db;
@@ -1280,14 +1335,15 @@ hipError_t launch_joint_reduce(const DevProblem &p, const JointArgs &j_in, const
     return e != hipSuccess ? e : hipGetLastError();
 }
 
-// kernel of a launch shape: MF = the backward's MFMA tile (32: 32x32x16, 16: 16x16x32); the forward runs 32x32x16
-template <int KS, int NB, int NW, int MF, bool BWD, int RG>
+// kernel of a launch shape: MF = the backward's MFMA tile (32: 32x32x16, 16: 16x16x32); the forward runs 32x32x16;
+// RC = the backward's row coefficients (LossCoef / PathCoef)
+template <int KS, int NB, int NW, int MF, bool BWD, int RG, class RC>
 static hipError_t launch_knw(const DevProblem &p, const JointArgs &j, size_t lds, hipStream_t stream) {
     const int64_t blocks = (j.n + 32 * NW - 1) / (32 * NW);
     if (blocks * 64 * NW > 0xffffffffll) return hipErrorInvalidValue;  // 32-bit dispatch size in work-items
     void (*kern)(DevProblem, JointArgs);
-    if constexpr (MF == 16 && BWD) kern = joint_bwd16_kernel<KS, NB, NW>;
-    else if constexpr (BWD) kern = joint_bwd_kernel<KS, NB, NW, RG>;
+    if constexpr (MF == 16 && BWD) kern = joint_bwd16_kernel<KS, NB, NW, RC>;
+    else if constexpr (BWD) kern = joint_bwd_kernel<KS, NB, NW, RG, RC>;
     else {
         kern = joint_fwd_kernel<KS, NB, NW, RG>;
         if constexpr (kVariants)
@@ -1306,7 +1362,7 @@ static hipError_t launch_knw(const DevProblem &p, const JointArgs &j, size_t lds
 // removed, DESIGN.md §4a: three buffers, two 4-wave workgroups per CU, deeper A-fragment rings, the forward on the
 // 16x16x32 tile, a persistent forward, the pipelined one-wave-per-SIMD forward, the bias as the initial accumulator
 // and the label logit as a dot product.)
-template <int KS, int MF, bool BWD>
+template <int KS, int MF, bool BWD, class RC>
 static hipError_t launch_kt(const DevProblem &p, const JointArgs &j, hipStream_t stream) {
     // the 16x16x32 backward with dbias keeps one row of column sums per wave (8) behind the bias; the forward a
     // bias * log2 e row (JointArgs::opt bit 1) where both rows fit, the unscaled epilogue otherwise
@@ -1316,25 +1372,27 @@ static hipError_t launch_kt(const DevProblem &p, const JointArgs &j, hipStream_t
     if (!BWD && 2 * tile + 2 * row > 160 * 1024) jj.opt &= ~2;
     const size_t bias = row * ((MF == 16 && BWD && j.dbias) ? 9 : (!BWD && (jj.opt & 2)) ? 2 : 1);
     if (j.dbias && !(MF == 16 && BWD)) return hipErrorInvalidValue;
-    if (2 * tile + bias <= 160 * 1024) return launch_knw<KS, 2, 8, MF, BWD, 2>(p, jj, 2 * tile + bias, stream);
+    if (2 * tile + bias <= 160 * 1024) return launch_knw<KS, 2, 8, MF, BWD, 2, RC>(p, jj, 2 * tile + bias, stream);
     return hipErrorInvalidValue;
 }
 
 // The backward's MFMA tile: 16x16x32 for H <= 512 (its epilogue carries no per-row running state, and there the
 // 16x16 tile's higher clock pays), 32x32x16 at H = 640 (the 16x16 one spills there: two rows' state per lane beside
 // 160 B-operand registers); the development build can force 32x32x16 (joint_bwd_mfma = 32).
-template <int KS, bool BWD>
+template <int KS, bool BWD, class RC>
 static hipError_t launch_kb(const DevProblem &p, const JointArgs &j, hipStream_t stream) {
     constexpr int kDefault = KS > 32 ? 32 : BWD ? Tuning{}.joint_bwd_mfma : 32;
     if constexpr (kVariants && KS <= 32 && BWD) {
-        if (tuning().joint_bwd_mfma == 32) return launch_kt<KS, 32, BWD>(p, j, stream);
+        if (tuning().joint_bwd_mfma == 32) return launch_kt<KS, 32, BWD, RC>(p, j, stream);
     }
-    return launch_kt<KS, kDefault, BWD>(p, j, stream);
+    return launch_kt<KS, kDefault, BWD, RC>(p, j, stream);
 }
 
+// pass: 0 forward, 1 the loss's gradient pass, 2 the path scores' (PathCoef)
 template <int KS>
-static hipError_t launch_kh(const DevProblem &p, const JointArgs &j, bool bwd, hipStream_t stream) {
-    return bwd ? launch_kb<KS, true>(p, j, stream) : launch_kb<KS, false>(p, j, stream);
+static hipError_t launch_kh(const DevProblem &p, const JointArgs &j, int pass, hipStream_t stream) {
+    if (pass == 2) return launch_kb<KS, true, PathCoef>(p, j, stream);
+    return pass ? launch_kb<KS, true, LossCoef>(p, j, stream) : launch_kb<KS, false, LossCoef>(p, j, stream);
 }
 
 size_t joint_min_lds_bytes(int H, int V) {  // two weight tiles + the bias row
@@ -1345,14 +1403,14 @@ size_t joint_dbias_lds_bytes(int H, int V) {  // the 16x16x32 backward with dbia
     return joint_min_lds_bytes(H, V) + 8 * sizeof(float) * (((size_t)V + 31) / 32 * 32);
 }
 
-static hipError_t launch_joint(const DevProblem &p, const JointArgs &j, bool bwd, hipStream_t stream) {
+static hipError_t launch_joint(const DevProblem &p, const JointArgs &j, int pass, hipStream_t stream) {
     if (j.n <= 0) return hipSuccess;
     switch (j.H) {
-        case 128: return launch_kh<8>(p, j, bwd, stream);
-        case 256: return launch_kh<16>(p, j, bwd, stream);
-        case 384: return launch_kh<24>(p, j, bwd, stream);
-        case 512: return launch_kh<32>(p, j, bwd, stream);
-        case 640: return launch_kh<40>(p, j, bwd, stream);
+        case 128: return launch_kh<8>(p, j, pass, stream);
+        case 256: return launch_kh<16>(p, j, pass, stream);
+        case 384: return launch_kh<24>(p, j, pass, stream);
+        case 512: return launch_kh<32>(p, j, pass, stream);
+        case 640: return launch_kh<40>(p, j, pass, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1415,13 +1473,13 @@ hipError_t launch_joint_forward(const DevProblem &p, const JointArgs &j, hipStre
         JointArgs jp = j;
         jp.probe = tuning().joint_probe;
         if (jp.probe & 8) jp.wplain = nullptr;  // (A/B: the running-max epilogue whatever the bound)
-        return launch_joint(p, jp, false, stream);
+        return launch_joint(p, jp, 0, stream);
     }
-    return launch_joint(p, j, false, stream);
+    return launch_joint(p, j, 0, stream);
 }
 
-hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream) {
-    return launch_joint(p, j, true, stream);
+hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream, bool path_coef) {
+    return launch_joint(p, j, path_coef ? 2 : 1, stream);
 }
 
 }  // namespace mrnnt

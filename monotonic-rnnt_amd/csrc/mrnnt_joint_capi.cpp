@@ -1,7 +1,9 @@
 // mrnnt_joint_capi.cpp -- the fused joint network + loss ABI of libmonotonic_rnnt_amd.so (mrnnt_joint_* in
 // include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint.hip,
 // mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors / mrnnt_joint_sample put the Viterbi launch / the
-// posterior read-out / the path sampler of the loss ABI behind the joint's log-softmax pass. Asynchronous on the caller's stream, no host synchronisation.
+// posterior read-out / the path sampler of the loss ABI behind the joint's log-softmax pass; mrnnt_joint_path_* score
+// given alignments (mrnnt_path.hip's walk / hull / score / coef launches around the joint pass over the hull rows) and
+// run the gradient pass over the path-live rows. Asynchronous on the caller's stream, no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -151,6 +153,107 @@ RNNTStatus joint_log_softmax(const mrnnt_joint_problem *jp, const JointPlan &jl,
     return RNNT_STATUS_SUCCESS;
 }
 
+// mrnnt_joint_path_*: the ordinary joint workspace of the same problem (make_joint_plan of jp, which has no alignment),
+// FOLLOWED by the band arrays (the hull of the paths) and the per-path words. mrnnt_joint_reduce / _reduce_pre / _dpre
+// rebuild the ordinary plan from jp and carve the workspace by its offsets: they work on this one unchanged.
+struct JointPathPlan {
+    JointPlan jl;
+    int64_t row_bound = 0;  // sum_b min(num_paths * T_b, in-band rows of b) >= the path-live rows
+    size_t off_min = 0, off_max = 0, off_valid = 0, off_carry = 0, total = 0;
+};
+
+// The plan and the host checks of the joint path entry points, all before any device call (make_path_plan's).
+RNNTStatus make_joint_path_plan(const mrnnt_joint_problem *jp, int num_paths, JointPathPlan *pp) {
+    if (jp && jp->alignment)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL: "
+                                               "the band arrays hold the hull of the given paths)");
+    if (num_paths < 1)
+        return fail(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
+    const RNNTStatus st = make_joint_plan(jp, &pp->jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = pp->jl.base;
+    if ((int64_t)pl.B * num_paths > 0x7fffffff || pl.B > 65535)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take B <= 65535 and B * num_paths < 2^31");
+    pp->row_bound = 0;
+    for (int b = 0; b < jp->B; ++b) {
+        const int T = jp->T_host[b], S = jp->S_host[b];
+        int64_t inband = 0;
+        for (int t = 0; t < T; ++t) inband += std::min(t, S) - std::max(0, t - (T - S)) + 1;
+        pp->row_bound += std::min<int64_t>((int64_t)num_paths * T, inband);
+    }
+    size_t o = pp->jl.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes);
+        return at;
+    };
+    pp->off_min = take(sizeof(int) * (size_t)pl.cols);
+    pp->off_max = take(sizeof(int) * (size_t)pl.cols);
+    pp->off_valid = take(sizeof(int) * (size_t)pl.B * num_paths);
+    pp->off_carry = take(sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
+    pp->total = o;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// the device problem with the hull as its band, and the path words
+DevProblem joint_path_dev(const mrnnt_problem *p, const JointPathPlan &pp, void *ws) {
+    DevProblem d = make_dev(p, pp.jl.base, ws);
+    d.min_s = carve<int>(ws, pp.off_min);
+    d.max_s = carve<int>(ws, pp.off_max);
+    return d;
+}
+
+PathArgs joint_path_args(const JointPathPlan &pp, void *ws, const int *alignments_dev, int num_paths,
+                         int64_t path_stride) {
+    return path_args(ws, pp.off_valid, pp.off_carry, pp.off_min, pp.off_max, alignments_dev, num_paths, path_stride);
+}
+
+// mrnnt_joint_backward / mrnnt_joint_path_backward: the MFMA gradient pass over the rows of the last list built, with
+// the loss's row coefficients (alpha / beta / ll, times scale) or the path weights (path: Wb / We in alpha / beta).
+RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale, void *G,
+                          void *Hact, int64_t *bt_idx, int64_t *bs_idx, bool path, hipStream_t stream) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (path && jp->alignment)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL)");
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
+    if (n_live < 0 || n_live > jl.n_inband)
+        return fail(RNNT_STATUS_INVALID_VALUE, "n_live outside [0, in-band rows]");
+    if (n_live > 0 && (!G || !Hact)) return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact is null");
+    if (n_live > 0 && (!aligned16(G) || !aligned16(Hact)))
+        return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact must be 16-byte aligned");
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = make_dev(&p, jl.base, ws);
+    JointArgs j = joint_args(jp, jl, ws, n_live);
+    j.n_dev = jp->live_count_dev;  // n_live a host bound: workgroups past the device count exit (their rows zeroed below)
+    j.G = static_cast<unsigned short *>(G);
+    j.Hact = static_cast<unsigned short *>(Hact);
+    j.bt_idx = bt_idx;
+    j.bs_idx = bs_idx;
+    j.scale = grad_scale;
+    j.dbias = jp->dbias;
+    if (jp->dbias && jp->H > 512) return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass needs H <= 512");
+    if (jp->dbias && joint_dbias_lds_bytes(jp->H, jp->V) > 160 * 1024)
+        return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass: V too large for its LDS column sums at this H "
+                                               "(sum G's columns outside: dbias = NULL)");
+    if (jp->dbias && !jl.off_dbias)
+        return fail(RNNT_STATUS_INVALID_VALUE, "dbias needs a bias (the workspace holds its partial sums only then)");
+    if (jp->dbias) j.dbias_part = carve<float>(ws, jl.off_dbias);
+    hipError_t e = timed(K_JOINT_BWD, stream, [&] {
+        const hipError_t eb = launch_joint_backward(d, j, stream, path);
+        if (eb != hipSuccess || !jp->live_count_dev) return eb;
+        return launch_joint_tail_zero(j.G, jp->V, j.Hact, j.hact_ld, n_live, jp->live_count_dev, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint gradient kernel");
+    if (jp->dbias && n_live > 0) {
+        e = launch_joint_dbias_sum(j, jp->V, stream);
+        if (e != hipSuccess) return fail_hip(e, "joint dbias sum kernels");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -263,44 +366,94 @@ RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *jp, void *ws, unsign
 
 RNNTStatus mrnnt_joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale,
                                 void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
-    JointPlan jl;
-    RNNTStatus st = make_joint_plan(jp, &jl);
+    return joint_backward(jp, ws, n_live, grad_scale, G, Hact, bt_idx, bs_idx, false, stream);
+}
+
+RNNTStatus mrnnt_joint_path_workspace_size(const mrnnt_joint_problem *jp, int num_paths, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    JointPathPlan pp;
+    const RNNTStatus st = make_joint_path_plan(jp, num_paths, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = pp.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_path_row_bound(const mrnnt_joint_problem *jp, int num_paths, int64_t *rows) {
+    if (!rows) return fail(RNNT_STATUS_INVALID_VALUE, "null rows pointer");
+    JointPathPlan pp;
+    const RNNTStatus st = make_joint_path_plan(jp, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *rows = pp.row_bound;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_path_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                    int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream) {
+    JointPathPlan pp;
+    RNNTStatus st = make_joint_path_plan(jp, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const JointPlan &jl = pp.jl;
+    const Plan &pl = jl.base;
+    if ((st = check_paths(pl, alignments_dev, path_stride)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
-    if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
-    if (n_live < 0 || n_live > jl.n_inband)
-        return fail(RNNT_STATUS_INVALID_VALUE, "n_live outside [0, in-band rows]");
-    if (n_live > 0 && (!G || !Hact)) return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact is null");
-    if (n_live > 0 && (!aligned16(G) || !aligned16(Hact)))
-        return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact must be 16-byte aligned");
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     const mrnnt_problem p = base_problem(jp);
-    DevProblem d = make_dev(&p, jl.base, ws);
-    JointArgs j = joint_args(jp, jl, ws, n_live);
-    j.n_dev = jp->live_count_dev;  // n_live a host bound: workgroups past the device count exit (their rows zeroed below)
-    j.G = static_cast<unsigned short *>(G);
-    j.Hact = static_cast<unsigned short *>(Hact);
-    j.bt_idx = bt_idx;
-    j.bs_idx = bs_idx;
-    j.scale = grad_scale;
-    j.dbias = jp->dbias;
-    if (jp->dbias && jp->H > 512) return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass needs H <= 512");
-    if (jp->dbias && joint_dbias_lds_bytes(jp->H, jp->V) > 160 * 1024)
-        return fail(RNNT_STATUS_INVALID_VALUE, "dbias in the gradient pass: V too large for its LDS column sums at this H "
-                                               "(sum G's columns outside: dbias = NULL)");
-    if (jp->dbias && !jl.off_dbias)
-        return fail(RNNT_STATUS_INVALID_VALUE, "dbias needs a bias (the workspace holds its partial sums only then)");
-    if (jp->dbias) j.dbias_part = carve<float>(ws, jl.off_dbias);
-    hipError_t e = timed(K_JOINT_BWD, stream, [&] {
-        const hipError_t eb = launch_joint_backward(d, j, stream);
-        if (eb != hipSuccess || !jp->live_count_dev) return eb;
-        return launch_joint_tail_zero(j.G, jp->V, j.Hact, j.hact_ld, n_live, jp->live_count_dev, stream);
+    DevProblem d = joint_path_dev(&p, pp, ws);  // d.min_s / d.max_s: the hull
+    LatticeOpts o;
+    o.t_cap = path_stride;
+    if ((st = prepare_lattice(&p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
+    PathArgs a = joint_path_args(pp, ws, alignments_dev, num_paths, path_stride);
+    a.costs = path_costs_dev;
+    hipError_t e = timed(K_DP, stream, [&] { return launch_path_walk(d, a, pl.T_max, stream); });
+    if (e != hipSuccess) return fail_hip(e, "path walk kernels");
+    // the hull rows, listed through the alignment window (mode 0); their number stays on the device. No lp zero fill:
+    // no recursion runs, and the score kernel reads lp along the valid walks only -- rows of the hull
+    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
+    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
+                        total, stream);
+    if (e != hipSuccess) return fail_hip(e, "row list kernels");
+    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
+    j.n_dev = total;
+    int *wplain = carve<int>(ws, jl.off_wplain);
+    j.wplain = wplain;
+    e = timed(K_JOINT_FWD, stream, [&] {
+        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
+        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
     });
-    if (e != hipSuccess) return fail_hip(e, "joint gradient kernel");
-    if (jp->dbias && n_live > 0) {
-        e = launch_joint_dbias_sum(j, jp->V, stream);
-        if (e != hipSuccess) return fail_hip(e, "joint dbias sum kernels");
+    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    if (path_costs_dev) {
+        e = timed(K_DP, stream, [&] { return launch_path_score(d, a, stream); });
+        if (e != hipSuccess) return fail_hip(e, "path score kernel");
     }
     return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_path_rows(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                 int num_paths, int64_t path_stride, const float *weights_dev,
+                                 unsigned long long *count_dev, hipStream_t stream) {
+    JointPathPlan pp;
+    RNNTStatus st = make_joint_path_plan(jp, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const JointPlan &jl = pp.jl;
+    if ((st = check_paths(jl.base, alignments_dev, path_stride)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if (!count_dev) return fail(RNNT_STATUS_INVALID_VALUE, "count is null");
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = joint_path_dev(&p, pp, ws);
+    PathArgs a = joint_path_args(pp, ws, alignments_dev, num_paths, path_stride);
+    a.w = weights_dev;
+    hipError_t e = timed(K_DP, stream, [&] { return launch_path_coef(d, a, jl.base.T_max, stream); });
+    if (e != hipSuccess) return fail_hip(e, "path coefficient kernel");
+    e = launch_row_list(d, 2, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
+                        count_dev, stream);
+    if (e != hipSuccess) return fail_hip(e, "path-live row list kernels");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_path_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_rows, void *G, void *Hact,
+                                     int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
+    return joint_backward(jp, ws, n_rows, nullptr, G, Hact, bt_idx, bs_idx, true, stream);
 }
 
 // pre: dH already holds dpre (Hact unused; the kRedPre kernel form)

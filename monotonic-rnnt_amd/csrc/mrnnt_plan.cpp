@@ -420,6 +420,27 @@ RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws
     return RNNT_STATUS_SUCCESS;
 }
 
+RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride) {
+    if (!alignments_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignments is null");
+    // with device lengths T_b <= path_stride joins the device validation
+    return check_row_stride("alignments", path_stride, "input", pl.T_max, pl.dyn, 1);
+}
+
+PathArgs path_args(void *ws, size_t off_valid, size_t off_carry, size_t off_min, size_t off_max,
+                   const int *alignments_dev, int num_paths, int64_t path_stride) {
+    PathArgs a;
+    a.al = alignments_dev;
+    a.stride = path_stride;
+    a.K = num_paths;
+    a.valid = carve<int>(ws, off_valid);
+    a.carry = carve<int>(ws, off_carry);
+    a.min_s = carve<int>(ws, off_min);
+    a.max_s = carve<int>(ws, off_max);
+    a.costs = nullptr;
+    a.w = nullptr;
+    return a;
+}
+
 // ---- profiling ---------------------------------------------------------------------------------
 
 static std::mutex g_prof_mu;

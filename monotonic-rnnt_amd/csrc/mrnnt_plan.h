@@ -106,6 +106,13 @@ RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws
                           int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
                           hipStream_t stream);
 
+// mrnnt_path_* / mrnnt_joint_path_*: the host check of the caller's alignment rows (non-NULL, path_stride >= max T_b;
+// with device lengths T_b <= path_stride joins the device validation), and the path launches' arguments over a
+// workspace that holds the per-path words and the hull (band) arrays at the given offsets.
+RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride);
+PathArgs path_args(void *ws, size_t off_valid, size_t off_carry, size_t off_min, size_t off_max,
+                   const int *alignments_dev, int num_paths, int64_t path_stride);
+
 // ---- profiling (mrnnt_profile_enable / mrnnt_profile_read) ------------------------------------------------------
 struct ProfRec {
     int id;

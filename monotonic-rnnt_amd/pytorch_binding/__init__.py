@@ -1,6 +1,8 @@
 """PyTorch surface of the MI355X monotonic RNN-T loss (drop-in for the reference's pytorch_binding)."""
-from .monotonic_rnnt_joint import (MonotonicRNNTJointFunction, monotonic_rnnt_joint_align, monotonic_rnnt_joint_loss,
-                                   monotonic_rnnt_joint_posteriors, monotonic_rnnt_joint_sample)
+from .monotonic_rnnt_joint import (MonotonicRNNTJointFunction, MonotonicRNNTJointPathFunction,
+                                   monotonic_rnnt_joint_align, monotonic_rnnt_joint_loss,
+                                   monotonic_rnnt_joint_path_loss, monotonic_rnnt_joint_posteriors,
+                                   monotonic_rnnt_joint_sample)
 from .monotonic_rnnt_op import (MonotonicRNNTFunction, MonotonicRNNTLoss, MonotonicRNNTPathFunction,
                                 monotonic_rnnt_align, monotonic_rnnt_cpp, monotonic_rnnt_loss, monotonic_rnnt_path_loss,
                                 monotonic_rnnt_posteriors, monotonic_rnnt_sample)
@@ -9,4 +11,4 @@ __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", 
            "MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_align",
            "monotonic_rnnt_posteriors", "monotonic_rnnt_joint_align", "monotonic_rnnt_joint_posteriors",
            "monotonic_rnnt_sample", "monotonic_rnnt_joint_sample", "MonotonicRNNTPathFunction",
-           "monotonic_rnnt_path_loss"]
+           "monotonic_rnnt_path_loss", "MonotonicRNNTJointPathFunction", "monotonic_rnnt_joint_path_loss"]

@@ -173,6 +173,11 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_joint_reduce_scratch_bytes": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_row_bound": (i, [JP, ctypes.POINTER(i64)]),
         "mrnnt_joint_dpre": (i, [JP, i64, vp, vp, vp, vp, vp]),
+        "mrnnt_joint_path_workspace_size": (i, [JP, i, ctypes.POINTER(sz)]),
+        "mrnnt_joint_path_row_bound": (i, [JP, i, ctypes.POINTER(i64)]),
+        "mrnnt_joint_path_forward": (i, [JP, vp, sz, vp, i, i64, vp, vp]),
+        "mrnnt_joint_path_rows": (i, [JP, vp, sz, vp, i, i64, vp, vp, vp]),
+        "mrnnt_joint_path_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp]),
         "mrnnt_last_error": (ctypes.c_char_p, []),
         "mrnnt_version": (i, []),
         "mrnnt_fill_zero": (i, [vp, sz, vp]),

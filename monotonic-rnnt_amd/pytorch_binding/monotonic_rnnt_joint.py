@@ -22,6 +22,12 @@ one pass. MRNNT_JOINT_DH=mfma (H = 256 / 512, V % 8 == 0) forms dpre in one hand
 are monotonic_rnnt_align / monotonic_rnnt_posteriors of the same never-stored logits: the joint log-softmax pass, then
 the Viterbi launch in the recursion's place, or the recursion with beta and the posterior read-out.
 
+    path_costs = monotonic_rnnt_joint_path_loss(enc, pred, weight, bias, labels, input_lengths, label_lengths, alignments)
+
+is monotonic_rnnt_path_loss of those logits: -log p of K given alignments per utterance, differentiable in enc, pred,
+weight and bias. Its forward computes the lattice rows between the lowest and the highest path of each frame and
+nothing else; its backward runs the chain above over the rows the paths stand on (at most K * T_b per utterance).
+
 Shapes: enc [B, T_slots >= max T, H], pred [B, S_slots >= max S + 1, H], weight [V, H] (torch.nn.Linear
 layout), bias [V] or None; H in {128, 256, 384, 512, 640}. Inputs of other floating dtypes are cast to bf16
 (the cast is differentiable, so their gradients come back in their own dtype). Costs are fp32 on the device.
@@ -195,6 +201,61 @@ class _JointPrepared:
             return G[:n], Hact[:n], bt[:n], bs[:n]
         return G[:n], Hact[:n]
 
+    def path_forward(self, al):
+        """(path_costs [B, K], workspace): mrnnt_joint_path_forward of the alignment rows al (int32 [B, K, L],
+        contiguous, on the device) on a workspace of mrnnt_joint_path_workspace_size bytes."""
+        lib = _L.load()
+        K, L = al.size(1), al.size(2)
+        n = ctypes.c_size_t(0)
+        _L.check(lib.mrnnt_joint_path_workspace_size(ctypes.byref(self.problem), K, ctypes.byref(n)),
+                 "joint_path_workspace_size")
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            costs = torch.empty((self.B, K), dtype=torch.float32, device=self.device)
+            _L.check(lib.mrnnt_joint_path_forward(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(al), K, L,
+                                                  _vp(costs), self.stream()), "mrnnt_joint_path_forward")
+        return costs, ws
+
+    def path_rows(self, ws, al, w):
+        """After path_forward: the path weights w (fp32 [B, K] on the device, or None = 1) become Wb / We, and the
+        path-live rows are listed; returns their count (int64 [1], on the device)."""
+        with torch.cuda.device(self.device):
+            cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+            _L.check(_L.load().mrnnt_joint_path_rows(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(al),
+                                                     al.size(1), al.size(2), _vp(w), _vp(cnt), self.stream()),
+                     "mrnnt_joint_path_rows")
+        return cnt
+
+    def path_row_bound(self, K):
+        nb = ctypes.c_int64(0)
+        _L.check(_L.load().mrnnt_joint_path_row_bound(ctypes.byref(self.problem), K, ctypes.byref(nb)),
+                 "joint_path_row_bound")
+        return nb.value
+
+    def path_backward_rows(self, ws, al, w, bias_column=False, dbias=None, capturable=False):
+        """backward_rows for the path scores: (G [n, V], Hact [n, H or _HACT_LD[H]]) over the path-live rows. By
+        default one 8-byte read-back of their count sizes the buffers; capturable: they are sized by the host-known
+        bound sum_b min(K T_b, in-band rows) (mrnnt_joint_path_row_bound), the kernels take the count from the device
+        and the rows past it are zeros."""
+        lib = _L.load()
+        cnt = self.path_rows(ws, al, w)
+        with torch.cuda.device(self.device):
+            if capturable:
+                n = self.path_row_bound(al.size(1))
+                self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
+                self.problem.live_count_dev = cnt.data_ptr()
+            else:
+                n = int(cnt.item())
+                self.problem.live_count_dev = None
+            G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
+            ld = _HACT_LD[self.H] if bias_column else self.H
+            self.problem.hact_ld = ld
+            Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
+            self.problem.dbias = _vp(dbias)
+            _L.check(lib.mrnnt_joint_path_backward(ctypes.byref(self.problem), _vp(ws), n, _vp(G), _vp(Hact), None,
+                                                   None, self.stream()), "mrnnt_joint_path_backward")
+        return G[:n], Hact[:n]
+
     def dpre(self, G, Hact):
         """dpre = (G weight) * (1 - Hact^2), bf16 [n, H], on the library's hand-written MFMA tiles (mrnnt_joint_dpre)."""
         n = G.shape[0]
@@ -310,42 +371,60 @@ class MonotonicRNNTJointFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_costs):
         prep, ws = ctx.prep, ctx.saved_tensors[3]
-        need_b = ctx.bias_dtype is not None and ctx.needs_input_grad[3]
-        # dbias rides on the dweight GEMM (a ones column in Hact); MRNNT_JOINT_BIAS_SUM=1: a separate G.sum (A/B)
-        in_pass = need_b and not _BIAS_SUM and _dbias_in_pass(prep.H, prep.V)
-        bias_col = need_b and ctx.needs_input_grad[2] and not _BIAS_SUM and prep.H in _HACT_LD and not in_pass
-        # the 16x16x32 gradient pass (H <= 512, LDS permitting) sums G's columns itself: no separate pass over G
-        fused_b = (need_b and not bias_col and not _BIAS_SUM and _bwd_sums_columns(prep.H)
-                   and _dbias_lds_fits(prep.H, prep.V))
-        db = torch.zeros(prep.V, dtype=torch.float32, device=prep.device) if fused_b else None
-        # capturable (no host read of the live-row count): asked for, MRNNT_JOINT_CAPTURABLE=1, or inside HIP-graph capture
-        cap = ctx.capturable if ctx.capturable is not None else (_CAPTURABLE or torch.cuda.is_current_stream_capturing())
-        G, Hact = prep.backward_rows(ws, grad_costs, bias_column=bias_col, dbias=db, capturable=cap)
-        d_enc = d_pred = d_w = d_b = None
-        H = prep.H
-        if ctx.needs_input_grad[2]:
-            dw = _split_k_weight_grad(G, Hact)  # [V, H] (+ dbias, zeros when Hact is wider)
-            d_w = dw[:, :H].to(prep.weight.dtype)
-            if bias_col:
-                d_b = dw[:, H].to(ctx.bias_dtype)
-        if fused_b:
-            d_b = db.to(ctx.bias_dtype)
-        elif need_b and not bias_col:
-            d_b = G.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            if _dpre_ok(H, prep.V):
-                # dpre = (G W) * (1 - Hact^2) in one hand-written MFMA pass; the reduce then reads it alone
-                dH, h_in = prep.dpre(G, Hact), None
-            else:
-                # [n, H] bf16 (hipBLASLt), with W^T stored [H, V] (1 MB copy): hipBLASLt's kernel for that layout runs
-                # 3.9 vs 4.4 ms at H = 512 (profiles/r04/joint/gemm_probe.json)
-                dH, h_in = G @ prep.weight.t().contiguous().t(), Hact
-            # G is dead once dH exists (dweight / dbias came first): the reduce's scratch (stream-ordered after the GEMM)
-            d_enc, d_pred = prep.reduce(ws, dH, h_in, ctx.needs_input_grad[0], ctx.needs_input_grad[1], scratch=G)
-            del G
-            d_enc = None if d_enc is None else d_enc.to(prep.enc.dtype)
-            d_pred = None if d_pred is None else d_pred.to(prep.pred.dtype)
-        return d_enc, d_pred, d_w, d_b, None, None, None, None, None, None, None
+        bias_col, fused_b, db = _dbias_plan(ctx, prep)
+        G, Hact = prep.backward_rows(ws, grad_costs, bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
+        return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 7
+
+
+def _capturable(ctx):
+    """capturable (no host read of the row count): asked for, MRNNT_JOINT_CAPTURABLE=1, or inside HIP-graph capture"""
+    if ctx.capturable is not None:
+        return ctx.capturable
+    return _CAPTURABLE or torch.cuda.is_current_stream_capturing()
+
+
+def _dbias_plan(ctx, prep):
+    """Where dbias comes from in a backward over row lists (the loss's and the path scores'): (bias_col, fused_b, db)."""
+    need_b = ctx.bias_dtype is not None and ctx.needs_input_grad[3]
+    # dbias rides on the dweight GEMM (a ones column in Hact); MRNNT_JOINT_BIAS_SUM=1: a separate G.sum (A/B)
+    in_pass = need_b and not _BIAS_SUM and _dbias_in_pass(prep.H, prep.V)
+    bias_col = need_b and ctx.needs_input_grad[2] and not _BIAS_SUM and prep.H in _HACT_LD and not in_pass
+    # the 16x16x32 gradient pass (H <= 512, LDS permitting) sums G's columns itself: no separate pass over G
+    fused_b = (need_b and not bias_col and not _BIAS_SUM and _bwd_sums_columns(prep.H)
+               and _dbias_lds_fits(prep.H, prep.V))
+    db = torch.zeros(prep.V, dtype=torch.float32, device=prep.device) if fused_b else None
+    return bias_col, fused_b, db
+
+
+def _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db):
+    """(d_enc, d_pred, d_weight, d_bias) from the gradient pass's rows G / Hact: the dweight GEMM, dbias, the dH GEMM
+    (or mrnnt_joint_dpre) and the reduce over the last row list built in ws."""
+    need_b = ctx.bias_dtype is not None and ctx.needs_input_grad[3]
+    d_enc = d_pred = d_w = d_b = None
+    H = prep.H
+    if ctx.needs_input_grad[2]:
+        dw = _split_k_weight_grad(G, Hact)  # [V, H] (+ dbias, zeros when Hact is wider)
+        d_w = dw[:, :H].to(prep.weight.dtype)
+        if bias_col:
+            d_b = dw[:, H].to(ctx.bias_dtype)
+    if fused_b:
+        d_b = db.to(ctx.bias_dtype)
+    elif need_b and not bias_col:
+        d_b = G.sum(0, dtype=torch.float32).to(ctx.bias_dtype)
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        if _dpre_ok(H, prep.V):
+            # dpre = (G W) * (1 - Hact^2) in one hand-written MFMA pass; the reduce then reads it alone
+            dH, h_in = prep.dpre(G, Hact), None
+        else:
+            # [n, H] bf16 (hipBLASLt), with W^T stored [H, V] (1 MB copy): hipBLASLt's kernel for that layout runs
+            # 3.9 vs 4.4 ms at H = 512 (profiles/r04/joint/gemm_probe.json)
+            dH, h_in = G @ prep.weight.t().contiguous().t(), Hact
+        # G is dead once dH exists (dweight / dbias came first): the reduce's scratch (stream-ordered after the GEMM)
+        d_enc, d_pred = prep.reduce(ws, dH, h_in, ctx.needs_input_grad[0], ctx.needs_input_grad[1], scratch=G)
+        del G
+        d_enc = None if d_enc is None else d_enc.to(prep.enc.dtype)
+        d_pred = None if d_pred is None else d_pred.to(prep.pred.dtype)
+    return d_enc, d_pred, d_w, d_b
 
 
 def monotonic_rnnt_joint_loss(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
@@ -362,6 +441,83 @@ def monotonic_rnnt_joint_loss(enc: torch.Tensor, pred: torch.Tensor, weight: tor
     return MonotonicRNNTJointFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
                                             label_lengths, blank_label, alignment, max_distance_from_alignment,
                                             capturable)
+
+
+class MonotonicRNNTJointPathFunction(torch.autograd.Function):
+    """Scores of given alignments under the fused joint, with gradients for enc, pred, weight and bias
+    (mrnnt_joint_path_forward / _rows / _backward, include/mrnnt.h): apply(enc, pred, weight, bias, labels,
+    input_lengths, label_lengths, alignments [B, K, L], blank_label=0, capturable=None) -> path_costs [B, K]. The
+    upstream gradient of path_costs is the kernels' signed weights w[b, k]."""
+
+    @staticmethod
+    def forward(ctx, enc, pred, weight, bias, labels, input_lengths, label_lengths, alignments, blank_label=0,
+                capturable=None):
+        prep = _JointPrepared(enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label)
+        al = alignments.detach()
+        if al.device != prep.device or al.dtype != torch.int32:
+            al = al.to(prep.device, torch.int32)
+        if al.dim() != 3 or al.size(0) != prep.B:
+            raise RuntimeError(f"monotonic_rnnt_joint_path_loss: alignments must be [B = {prep.B}, K, L], "
+                               f"got {tuple(al.shape)}")
+        al = al.contiguous()
+        if al.size(1) < 1 or al.size(2) < 1:
+            raise RuntimeError("monotonic_rnnt_joint_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got "
+                               f"{al.size(1)}, {al.size(2)}")
+        costs, ws = prep.path_forward(al)
+        if any(ctx.needs_input_grad[:4]):
+            # the workspace holds den of the hull rows, the hull and the paths' validity
+            ctx.save_for_backward(enc, pred, weight, ws, al)
+            ctx.prep = prep
+            ctx.bias_dtype = None if bias is None else bias.dtype
+            ctx.capturable = capturable
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_costs):
+        prep, ws, al = ctx.prep, ctx.saved_tensors[3], ctx.saved_tensors[4]
+        w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
+        bias_col, fused_b, db = _dbias_plan(ctx, prep)
+        G, Hact = prep.path_backward_rows(ws, al, w, bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
+        if G.shape[0] == 0:  # no path-live row (all-zero weights, no valid path): every gradient is exactly zero
+            need = ctx.needs_input_grad
+            zero = lambda x, dt: torch.zeros(x.shape, dtype=dt, device=prep.device)  # noqa: E731
+            d_b = zero(prep.bias, ctx.bias_dtype) if ctx.bias_dtype is not None and need[3] else None
+            return (zero(prep.enc, prep.enc.dtype) if need[0] else None,
+                    zero(prep.pred, prep.pred.dtype) if need[1] else None,
+                    zero(prep.weight, prep.weight.dtype) if need[2] else None, d_b) + (None,) * 6
+        return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 6
+
+
+def monotonic_rnnt_joint_path_loss(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                                   bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
+                                   label_lengths: torch.Tensor, alignments: torch.Tensor, blank_label: int = 0,
+                                   capturable: Optional[bool] = None) -> torch.Tensor:
+    """Differentiable scores of given alignments under the joint network tanh(enc + pred) @ weight.T + bias, without
+    materialising its logits: path_costs[b, k] = -log p(alignment (b, k)), monotonic_rnnt_path_loss of the acts
+    monotonic_rnnt_joint_loss never stores, with gradients for enc, pred, weight and bias (each in its own dtype).
+    What makes monotonic_rnnt_joint_align / monotonic_rnnt_joint_sample trainable -- Viterbi training (K = 1),
+    risk-weighted / MWER / REINFORCE objectives over sampled paths (the upstream gradient of a path cost may have either
+    sign), latency penalties:
+
+        s = monotonic_rnnt_joint_sample(enc, pred, weight, bias, labels, T, S, num_samples=8, seed=step)
+        pc = monotonic_rnnt_joint_path_loss(enc, pred, weight, bias, labels, T, S, s.alignments)   # [B, 8]
+        (risk(s.alignments).detach() * torch.softmax(-pc, 1)).sum().backward()
+
+    enc / pred / weight / bias / labels / lengths as monotonic_rnnt_joint_loss takes them (the bf16 cast, H in JOINT_H,
+    GPU only). alignments: int [B, K, L] (returns [B, K]) or [B, L] (returns [B]), L >= every T_b, in the format
+    monotonic_rnnt_joint_align / monotonic_rnnt_joint_sample return and monotonic_rnnt_path_loss consumes. A row that
+    is no path of its utterance (a wrong or negative label, a -1 sentinel row, too few or too many labels) costs +inf
+    and gets no gradient whatever its upstream gradient is. The forward computes only the lattice rows between the
+    lowest and the highest path of each frame; the backward runs the joint's chain (MFMA gradient pass, dweight / dH
+    GEMMs, reduce) over the rows some path with a non-zero weight stands on -- at most K * T_b per utterance -- and
+    writes no dense logit gradient. capturable as in monotonic_rnnt_joint_loss: by default one 8-byte read-back of
+    that row count sizes the row buffers; True (or inside HIP-graph capture) sizes them by the host-known bound
+    sum_b min(K T_b, in-band rows). Costs and gradients are bitwise reproducible."""
+    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
+    al = alignments.unsqueeze(1) if alignments.dim() == 2 else alignments
+    out = MonotonicRNNTJointPathFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
+                                               label_lengths, al, blank_label, capturable)
+    return out.squeeze(1) if alignments.dim() == 2 else out
 
 
 def _bf16(x):
@@ -436,4 +592,5 @@ def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: t
 
 
 __all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_joint_align",
-           "monotonic_rnnt_joint_posteriors", "monotonic_rnnt_joint_sample"]
+           "monotonic_rnnt_joint_posteriors", "monotonic_rnnt_joint_sample", "MonotonicRNNTJointPathFunction",
+           "monotonic_rnnt_joint_path_loss"]
