@@ -111,6 +111,23 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *workspace, size_t workspa
 RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *workspace, const float *grad_scale, void *grads,
                           hipStream_t stream);
 
+/* (an addition to version 13: MRNNT_VERSION and both structs are unchanged) mrnnt_backward into a buffer whose
+ * contents the caller can vouch for, so that rows which already hold the zero they would get are not stored again.
+ * row_state: device memory, one byte per row of grads (rows of p->V elements of the acts type, in the layout of
+ * acts), row_state_len of them. On entry the caller vouches, per row:
+ *     0  unknown        1  every element of the row is +0.0        2  every element of the row is -0.0
+ * In stream order on return grads holds, bit for bit, what mrnnt_backward would have written; row_state describes
+ * the new contents of every row the call covers (0 for a row with a gradient or NaN, 1 / 2 for a row of +0 / -0;
+ * all 0 when device lengths failed validation and grads is NaN); bytes past the rows the call covers are not touched.
+ * A state byte that claims a zero the row does not hold gives a wrong gradient: whoever writes grads between two
+ * calls must reset the bytes of the rows written (all 0 is always safe). grads must not alias acts.
+ * row_state == NULL is exactly mrnnt_backward. row_state_len smaller than the rows covered (num_rows; padded layout:
+ * B * pad_T * pad_S1) gives RNNT_STATUS_INVALID_VALUE before any device call. Rows are skipped by the vectorised
+ * default kernel; the other gradient kernels (V or a pointer not 16-byte aligned; streamed rows of < 96 vectors)
+ * write every row and leave the covered state 0. */
+RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *workspace, const float *grad_scale, void *grads,
+                                  unsigned char *row_state, int64_t row_state_len, hipStream_t stream);
+
 /* forward(with_beta = grads != NULL) followed by backward. */
 RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, float *costs_dev,
                                void *grads, const float *grad_scale, hipStream_t stream);
@@ -240,6 +257,12 @@ RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *workspace, size_t wo
 RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
                                const int *alignments_dev, int num_paths, int64_t path_stride, const float *weights_dev,
                                void *grads, hipStream_t stream);
+/* (an addition to version 13) mrnnt_path_backward with the row state of mrnnt_backward_tracked: the same contract,
+ * the same bytes, so one buffer and one state can serve loss and path gradients in turn. */
+RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                       const int *alignments_dev, int num_paths, int64_t path_stride,
+                                       const float *weights_dev, void *grads, unsigned char *row_state,
+                                       int64_t row_state_len, hipStream_t stream);
 
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */

@@ -41,6 +41,14 @@ RNNTStatus plan_in_launch(const mrnnt_problem *p, const Plan &pl, int64_t scatte
 }
 
 // An asynchronous device-to-device copy into an output that may be NULL (then nothing to do).
+// The row state of the tracked backward entry points: one byte per row of grads the call covers.
+RNNTStatus check_row_state(const DevProblem &d, const unsigned char *row_state, int64_t row_state_len) {
+    if (row_state && row_state_len < grads_rows(d))
+        return fail(RNNT_STATUS_INVALID_VALUE, "row_state has " + std::to_string(row_state_len) + " bytes but the call covers " +
+                                                   std::to_string(grads_rows(d)) + " rows of grads");
+    return RNNT_STATUS_SUCCESS;
+}
+
 bool copy_out(void *dst, const void *src, size_t bytes, hipStream_t stream) {
     return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
 }
@@ -128,6 +136,11 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, floa
 
 RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
                           hipStream_t stream) {
+    return mrnnt_backward_tracked(p, ws, grad_scale, grads, nullptr, 0, stream);
+}
+
+RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                                  unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
     Plan pl;
     RNNTStatus st = make_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -135,6 +148,8 @@ RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *ws, const float *g
     if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
     if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
     DevProblem d = make_dev(p, pl, ws);
+    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
+    d.row_state = row_state;
     d.col_mul = column_order(pl, 2);
     // grad_variant 3 sweeps rows (packed layout only), the others walk lattice columns
     const int grid = (tuning().grad_variant == 3 && pl.pad_S1 == 0)
@@ -288,6 +303,13 @@ RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes,
 RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
                                int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
                                hipStream_t stream) {
+    return mrnnt_path_backward_tracked(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads,
+                                       nullptr, 0, stream);
+}
+
+RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                       int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                                       unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
     PathPlan pp;
     RNNTStatus st = make_path_plan(p, num_paths, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -297,6 +319,8 @@ RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes
     if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
     if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
+    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
+    d.row_state = row_state;
     PathArgs a = path_args(pp, ws, alignments_dev, num_paths, path_stride);
     a.w = weights_dev;
     hipError_t e = timed(K_DP, stream, [&] { return launch_path_coef(d, a, pl.T_max, stream); });

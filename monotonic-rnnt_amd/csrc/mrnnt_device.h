@@ -485,7 +485,8 @@ __device__ __forceinline__ RowCoef row_coef(const DevProblem &p, int t, int T, i
 }
 
 // Device-resident lengths that failed validation: every gradient element is NaN (the costs are NaN too), written
-// over the caller's whole grads buffer (rows as the host sized it) by the workgroups of the gradient launch.
+// over the caller's whole grads buffer (rows as the host sized it) by the workgroups of the gradient launch, and
+// every byte of the row state (DevProblem::row_state) becomes 0.
 template <class IO>
 __device__ __forceinline__ void fill_failed_grads(const DevProblem &p, void *grads) {
     typename IO::S *g = static_cast<typename IO::S *>(grads);
@@ -494,6 +495,9 @@ __device__ __forceinline__ void fill_failed_grads(const DevProblem &p, void *gra
     const typename IO::S nan = IO::from_f(__builtin_nanf(""));
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         g[i] = nan;
+    if (p.row_state)  // tracked launch: no row is known to be zero any more
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (int64_t)gridDim.x * blockDim.x)
+            p.row_state[i] = 0;
 }
 
 template <bool NT, class V>

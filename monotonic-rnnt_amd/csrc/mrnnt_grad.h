@@ -2,7 +2,7 @@
 // loss gradient (LossRows, mrnnt_grad.hip) and the path-score gradient (PathRows, mrnnt_path.hip). P supplies
 //   Col, column()   what a lattice column sets up once: its band of rows with a gradient; zero(): the other rows' value
 //   Slot, stage()   a row's coefficients as they are staged in LDS, two buffers of 256 slots (a dead slot: the row is
-//                   stored as zero()), live()
+//                   stored as zero()), live(); skip() / skipped(): a dead slot whose row already holds zero() (row state)
 //   Coef, coef()    a live slot's coefficients as the formula takes them; row(): the same without staging (false:
 //                   not live), for the scalar kernel
 //   grad_vec(), grad()   the per-vector formula and its scalar twin
@@ -16,6 +16,13 @@ namespace mrnnt {
 
 constexpr int kGradSeg = 256;  // rows per work unit of the staged kernel: one per thread in phase A
 constexpr int kDeadRow = -2;   // label word of a staged row whose gradient is exactly zero (out of band or dead)
+constexpr int kSkipRow = -3;   // ... and whose row of grads already holds that zero (p.row_state): not stored again
+
+// Row state (DevProblem::row_state, mrnnt_backward_tracked): the code of a row filled with the value z.
+__device__ __forceinline__ unsigned char zero_code(float z) {
+    const unsigned bits = __float_as_uint(z);
+    return bits == 0u ? 1 : (bits == 0x80000000u ? 2 : 0);  // +0, -0 (either survives the conversion to bf16 / f16)
+}
 
 // Staged-coefficient kernel (grad_variant 5, the default, and 6: 2 rows per wave). Work unit = a segment of up to 256
 // rows of one lattice column. Phase A: one row per thread, the row's coefficients (P::stage; the loss's row_coef reads
@@ -23,6 +30,8 @@ constexpr int kDeadRow = -2;   // label word of a staged row whose gradient is e
 // Phase B: the waves stream the segment's rows; a row's acts loads wait only for one broadcast LDS read, not for
 // a chain of dependent scalar loads and fp64 math, so every wave keeps its row(s) of acts in flight. Two LDS
 // buffers alternate between work units: one barrier per unit.
+// With p.row_state, phase A also keeps the row's state byte (every row is staged by exactly one thread of the grid):
+// a dead row whose byte already says "all zero(), same sign" is marked kSkipRow and phase B neither loads nor stores it.
 template <class IO, int U, int R, bool NTL, bool NTS, class P>
 __global__ __launch_bounds__(256) void grad_staged_kernel(DevProblem p, const float *__restrict__ scale,
                                                           void *__restrict__ grads) {
@@ -56,13 +65,21 @@ __global__ __launch_bounds__(256) void grad_staged_kernel(DevProblem p, const fl
         const int64_t arow = acts_col_base(p, b, t, rowc);
         const typename P::Col col = P::column(p, b, c, t, T, S);
         const float sc = scale ? scale[b * p.scale_stride] : 1.0f;  // upstream gradient of the utterance
-        const Vec zv = splat<IO>(P::zero(col, sc));
+        const float zf = P::zero(col, sc);
+        const Vec zv = splat<IO>(zf);
         const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
 
         for (int seg = 0; seg <= S; seg += SEG, buf ^= 1) {
             {  // phase A
                 const int s = seg + tid;
-                const Slot cf = P::stage(p, col, t, S, s, rowc, lab_b);
+                Slot cf = P::stage(p, col, t, S, s, rowc, lab_b);
+                if (p.row_state && s <= S) {
+                    unsigned char *st = p.row_state + (arow + s);
+                    const unsigned char code = P::live(cf) ? 0 : zero_code(zf);
+                    const unsigned char was = *st;
+                    if (code && was == code) P::skip(cf);
+                    if (was != code) *st = code;
+                }
                 if (s <= S) coef[buf][tid] = cf;
             }
             __syncthreads();
@@ -74,6 +91,7 @@ __global__ __launch_bounds__(256) void grad_staged_kernel(DevProblem p, const fl
                 for (int r = 0; r < R; ++r) {
                     ok[r] = i + r < n;
                     cf[r] = coef[buf][ok[r] ? i + r : i];
+                    ok[r] = ok[r] && !P::skipped(cf[r]);
                     live[r] = ok[r] && P::live(cf[r]);
                 }
                 for (int base = 0; base < VL; base += 64 * U) {
@@ -145,6 +163,12 @@ __global__ __launch_bounds__(256) void grad_scalar_kernel(DevProblem p, const fl
     }
 }
 
+// A launch of a kernel that does not keep the row state (every kernel but the staged one): the covered rows become
+// "unknown" before it runs, in stream order. (A failed memset is reported by the launch's hipGetLastError.)
+static inline void forget_row_state(const DevProblem &p, hipStream_t stream) {
+    if (p.row_state && grads_rows(p) > 0) (void)hipMemsetAsync(p.row_state, 0, (size_t)grads_rows(p), stream);
+}
+
 template <class IO>
 static bool vec_ok(const DevProblem &p, const void *grads) {
     return (p.V % IO::E) == 0 && (reinterpret_cast<uintptr_t>(p.acts) % 16) == 0 &&
@@ -166,6 +190,7 @@ static void launch_vec(const DevProblem &p, const float *scale, void *grads, int
 template <class P, class IO>
 static void launch_io(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
     if (!vec_ok<IO>(p, grads)) {
+        forget_row_state(p, stream);
         grad_scalar_kernel<IO, P><<<grid, 256, 0, stream>>>(p, scale, grads);
         return;
     }

@@ -46,7 +46,9 @@ struct LossRows {
         }
         return cf;
     }
-    static __device__ __forceinline__ bool live(const Slot &cf) { return __float_as_int(cf.w) != kDeadRow; }
+    static __device__ __forceinline__ bool live(const Slot &cf) { return __float_as_int(cf.w) > kDeadRow; }
+    static __device__ __forceinline__ void skip(Slot &cf) { cf.w = __int_as_float(kSkipRow); }
+    static __device__ __forceinline__ bool skipped(const Slot &cf) { return __float_as_int(cf.w) == kSkipRow; }
     static __device__ __forceinline__ Coef coef(const Slot &cf) {
         return RowCoef{cf.x, cf.y, cf.z, __float_as_int(cf.w), true};
     }
@@ -262,6 +264,10 @@ __global__ __launch_bounds__(256) void pad_zero_kernel(DevProblem p, void *__res
         const int b = (int)(bt / p.pad_T);
         const int t = (int)(bt - (int64_t)b * p.pad_T);
         if (t < p.T[b] && s <= p.S[b]) continue;
+        if (p.row_state) {  // tracked: a padding row that already holds +0 stays as it is; the others become +0
+            if (p.row_state[row] == 1) continue;  // (one byte, the same for every lane of the row's wave)
+            if (lane == 0) p.row_state[row] = 1;
+        }
         if (vec) {
             const int VL = V / IO::E;
             Vec *__restrict__ g = reinterpret_cast<Vec *>(grads) + row * (int64_t)VL;
@@ -278,13 +284,18 @@ __global__ __launch_bounds__(256) void pad_zero_kernel(DevProblem p, void *__res
 template <class IO, bool NTL, bool NTS, int U>
 void LossRows::launch_u(const DevProblem &p, const float *scale, void *grads, int grid, hipStream_t stream) {
     constexpr int RD = staged_rows(U);
+    // only the staged kernel keeps the row state (p.row_state); before any other, the covered rows become "unknown"
     if constexpr (!kVariants) {  // the product library: the tuned default (grad_variant 5) only
-        if constexpr (U == 1 && NTL)
+        if constexpr (U == 1 && NTL) {
+            forget_row_state(p, stream);
             grad_kernel<IO, U, 2, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
-        else
+        } else
             grad_staged_kernel<IO, U, RD, NTL, NTS, LossRows><<<grid, 256, 0, stream>>>(p, scale, grads);
     } else {
         const int variant = tuning().grad_variant;
+        const bool staged = !(variant == 3 && p.pad_S1 == 0) && variant != 0 && variant != 2 &&
+                            !(variant == 5 && U == 1 && NTL);
+        if (!staged) forget_row_state(p, stream);
         if (variant == 3 && p.pad_S1 == 0)
             grad_rows_kernel<IO, U, NTL, NTS><<<grid, 256, 0, stream>>>(p, scale, grads);
         else if (variant == 0)

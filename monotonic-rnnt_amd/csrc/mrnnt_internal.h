@@ -70,7 +70,13 @@ struct DevProblem {
     int64_t s_cap, t_cap, s1_cap;  // validation limits (S_b <= s_cap; T_b <= t_cap, S_b + 1 <= s1_cap when > 0)
     int64_t scatter_above;         // publish a scattered-order multiplier when there are more columns than this
     int *status_host;              // device address of the caller's host-mapped status word, or nullptr
+    // mrnnt_backward_tracked / mrnnt_path_backward_tracked: one byte per row of grads -- 0 unknown, 1 the row is all
+    // +0.0, 2 all -0.0 -- read and rewritten by the gradient launch (mrnnt_grad.h); nullptr: every row is written
+    unsigned char *row_state = nullptr;
 };
+
+// rows of the caller's grads buffer a gradient launch covers (host bound)
+inline int64_t grads_rows(const DevProblem &p) { return p.pad_S1 ? (int64_t)p.B * p.pad_T * p.pad_S1 : p.num_rows; }
 
 // Fused joint network (mrnnt_joint.hip): logits z(b,t,s,:) = W * tanh(enc[b,t,:] + pred[b,s,:]) + bias are
 // formed on MFMA inside the log-softmax and gradient passes and never stored. Operands are bf16 bit patterns.

@@ -224,7 +224,9 @@ struct PathRows {
         c = stage(p, col, t, S, s, rowc, lab_b);
         return live(c);
     }
-    static __device__ __forceinline__ bool live(const Slot &c) { return c.lab != kDeadRow; }
+    static __device__ __forceinline__ bool live(const Slot &c) { return c.lab > kDeadRow; }
+    static __device__ __forceinline__ void skip(Slot &c) { c.lab = kSkipRow; }
+    static __device__ __forceinline__ bool skipped(const Slot &c) { return c.lab == kSkipRow; }
     static __device__ __forceinline__ const Coef &coef(const Slot &c) { return c; }
 
     template <class IO>

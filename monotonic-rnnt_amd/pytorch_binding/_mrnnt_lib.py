@@ -138,6 +138,7 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_lattice_bytes": (i, [P, ctypes.POINTER(sz)]),
         "mrnnt_lattice_host": (i, [P, vp, sz]),
         "mrnnt_backward": (i, [P, vp, vp, vp, vp]),
+        "mrnnt_backward_tracked": (i, [P, vp, vp, vp, vp, i64, vp]),
         "mrnnt_cost_and_grad": (i, [P, vp, sz, vp, vp, vp, vp]),
         "mrnnt_read_loglik": (i, [P, vp, vp, vp, vp]),
         "mrnnt_grad_live_rows": (i, [P, vp, vp, vp]),
@@ -158,6 +159,7 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_path_workspace_size": (i, [P, i, ctypes.POINTER(sz)]),
         "mrnnt_path_forward": (i, [P, vp, sz, vp, i, i64, vp, vp]),
         "mrnnt_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, vp]),
+        "mrnnt_path_backward_tracked": (i, [P, vp, sz, vp, i, i64, vp, vp, vp, i64, vp]),
         "mrnnt_cpu_path_workspace_size": (i, [P, i, ctypes.POINTER(sz)]),
         "mrnnt_cpu_path_forward": (i, [P, vp, sz, vp, i, i64, vp, i]),
         "mrnnt_cpu_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, i]),

@@ -353,8 +353,10 @@ def _forward(prep: _Prepared, with_beta: bool):
 
 def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tensor],
               grads: Optional[torch.Tensor] = None) -> torch.Tensor:
-    if grads is None:  # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement)
-        grads = _GP.grads_like(prep.acts) if prep.on_gpu else torch.empty_like(prep.acts)
+    ticket = None
+    if grads is None:  # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), with the
+        # state of its rows: the tracked entry does not store again the zero rows the buffer already holds
+        grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
     prep.problem.grad_scale_broadcast = 0
     if grad_scale is not None:
         grad_scale = grad_scale.detach()
@@ -365,7 +367,12 @@ def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tens
             prep.problem.grad_scale_broadcast = 1
         else:
             grad_scale = grad_scale.to(prep.device, torch.float32).contiguous()
-    _call(prep, "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
+    if ticket is not None:
+        _call(prep, "backward_tracked", _ptr(ws), _ptr(grad_scale), _ptr(grads), _ptr(ticket.state),
+              ticket.state.numel(), lengths=False)
+        ticket.commit()  # enqueued: the state describes the buffer from here on (in stream order)
+    else:
+        _call(prep, "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
     return grads
 
 
@@ -593,8 +600,13 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
         K, L = al.size(1), al.size(2)
         w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
         # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), as the loss's
-        grads = _GP.grads_like(prep.acts) if prep.on_gpu else torch.empty_like(prep.acts)
-        _call(prep, "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads), lengths=False)
+        grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
+        if ticket is not None:  # (the row state, as the loss's _backward)
+            _call(prep, "path_backward_tracked", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
+                  _ptr(ticket.state), ticket.state.numel(), lengths=False)
+            ticket.commit()
+        else:
+            _call(prep, "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads), lengths=False)
         return grads, None, None, None, None, None
 
 

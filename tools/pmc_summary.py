@@ -21,6 +21,7 @@ import json
 import os
 import sys
 import shutil
+import statistics
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,8 +96,10 @@ def main():
     for name in sorted(set(fetch) | set(write)):
         if family(name) is None:
             continue
-        fk = sum(fetch.get(name, [0])) / max(1, len(fetch.get(name, [0])))
-        wk = sum(write.get(name, [0])) / max(1, len(write.get(name, [0])))
+        # the median launch: the launches of a kernel move the same bytes, except the gradient's first one in a
+        # process, which finds no row state to trust and writes every row
+        fk = statistics.median(fetch.get(name, [0]))
+        wk = statistics.median(write.get(name, [0]))
         per[short(name)] = {"FETCH_SIZE_KiB": fk, "WRITE_SIZE_KiB": wk, "launches": len(fetch.get(name, [])),
                             "hbm_bytes_corrected": fk * 1024 * 2 + wk * 1024,
                             "rocprof_avg_ms": next((v["avg_ms"] for k, v in stats.items() if short(k) == short(name)),
@@ -110,6 +113,8 @@ def main():
     assert grad and soft, per.keys()
     g, s = per[grad[0]], per[soft[0]]
     alg = bench["roofline"]["algorithmic_bytes_per_launch"]
+    steady = 2 * bench["roofline"]["live_rows"] * bench["config"]["V"] * elem + bench["config"]["rows_per_gpu"]
+    gfull = next(n for n in write if short(n) == grad[0])
     res = {
         "config": a.config,
         "dtype": a.dtype,
@@ -119,6 +124,11 @@ def main():
         "write_bytes": int(round(g["WRITE_SIZE_KiB"] * 1024)),
         "algorithmic_bytes_per_launch": alg,
         "traffic_over_algorithmic": round(g["hbm_bytes_corrected"] / alg, 4),
+        # with the row state in steady state the launch reads and writes the live rows only, plus one state byte per row
+        # read (and the changed ones written): 2 * live * V * elem + rows
+        "steady_state_bytes_per_launch": steady,
+        "traffic_over_steady_state": round(g["hbm_bytes_corrected"] / steady, 4),
+        "write_bytes_first_launch": int(round(max(write.get(gfull, [0])) * 1024)),
         "softmax_kernel": soft[0],
         "softmax_read_bytes_corrected": int(round(s["FETCH_SIZE_KiB"] * 2048)),
         "softmax_algorithmic_bytes": bench["config"]["inband_rows_per_gpu"] * bench["config"]["V"] * elem,
