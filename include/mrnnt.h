@@ -264,6 +264,59 @@ RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *workspace, 
                                        const float *weights_dev, void *grads, unsigned char *row_state,
                                        int64_t row_state_len, hipStream_t stream);
 
+/* Expected path costs with a gradient (an addition to version 13: MRNNT_VERSION and every struct are unchanged, so
+ * callers that may meet an older build of version 13 probe for the symbols mrnnt_expect_forward /
+ * mrnnt_cpu_expect_forward). For a cost that adds up over the arcs of a path -- emission time (expected latency), blank
+ * count, a per-arc risk -- the expectation under p(path | labels, acts) and its logit gradient are exact lattice
+ * quantities (the first-order expectation semiring): no sampling. Conventions as mrnnt_posteriors: alpha(t, s) after
+ * frame t (alpha(-1, s) = [s == 0]), beta(t, s) before frame t (beta(T, s) = [s == S]), ll = alpha(T-1, S); row (t, s)
+ * has a blank arc to (t+1, s) and, for s < S, a label arc to (t+1, s+1).
+ *   blank_cost_dev / label_cost_dev: wb / we, one fp32 per row of acts in acts' row layout -- the layout of
+ *       mrnnt_posteriors' blank_post / label_post: packed [N], or [B, pad_T, pad_S1]. Either may be NULL (all zeros).
+ *       we at s = S_b and anything at padding rows is never used. f(path) = sum_t cost(arc_t).
+ *   expected[b] = sum_path p(path) f(path) / sum_path p(path)      (= sum_rows blank_post wb + label_post we)
+ *   A(t, s)  = [e^(alpha(t-1,s)+lpb(t,s)) (A(t-1,s)+wb(t,s)) + e^(alpha(t-1,s-1)+lpe(t,s-1)) (A(t-1,s-1)+we(t,s-1))] / e^alpha(t,s)
+ *   Bk(t, s) = [e^(lpb(t,s)+beta(t+1,s)) (wb(t,s)+Bk(t+1,s)) + e^(lpe(t,s)+beta(t+1,s+1)) (we(t,s)+Bk(t+1,s+1))] / e^beta(t,s)
+ *   A(-1, .) = 0, Bk(T, .) = 0, R = expected[b] = A(T-1, S) = Bk(0, 0)
+ *   cb(t, s) = blank_post(t, s) (A(t-1, s) + wb(t, s) + Bk(t+1, s)   - R)
+ *   ce(t, s) = label_post(t, s) (A(t-1, s) + we(t, s) + Bk(t+1, s+1) - R)        (0 at s = S)
+ *   d expected / d z[r, v] = cb ([v == blank] - softmax(z_r)[v]) + ce ([v == label(s)] - softmax(z_r)[v])
+ * A and Bk are convex combinations (signed costs are fine), fp64 state, 0 on cells no path reaches; the two weights of
+ * a step sum to exactly 1. A single-path lattice (S = 0, S = T) has a zero gradient.
+ * mrnnt_expect_forward: mrnnt_forward (costs_dev[b] = the loss, may be NULL; with_grad: with beta) and then ONE launch
+ *   that carries A forward and -- with_grad -- Bk backward, concurrently; expected_dev[b] = fp32(R) (may be NULL).
+ * mrnnt_expect_backward (after mrnnt_expect_forward(with_grad = 1) on the same workspace, problem and costs): the logit
+ *   gradient of sum_b g_e[b] expected[b] + g_c[b] costs[b] in ONE dense pass (grad_expected_dev / grad_costs_dev: fp32
+ *   [B], either may be NULL = 0 for that term):
+ *       Wb = g_c blank_post - g_e cb,   We = g_c label_post - g_e ce
+ *       grads[r, v] = (Wb + We) softmax(z_r)[v] - [v == blank] Wb - [v == label(s)] We.
+ *   A row whose two fp32 coefficients are both zero (outside the band, unreachable, underflow) is stored as exact zeros
+ *   without reading its acts. Padding rows of the padded layout are 0. grads has the layout and element type of acts.
+ *   mrnnt_expect_backward_tracked: the same with the row state of mrnnt_backward_tracked (the same contract and bytes).
+ * An utterance whose ll is not finite has expected[b] NaN and every one of its gradient rows NaN (as the loss for
+ * ll = -inf); the other utterances are bit-identical to a call without it. Device-resident lengths that fail
+ * validation give NaN everywhere and raise *status_host, as the loss does. The cost arrays are not differentiated
+ * (their gradient is mrnnt_posteriors' blank_post / label_post). Every sum has a fixed order and no atomics: results
+ * are bitwise reproducible and do not depend on the other utterances.
+ * Takes everything mrnnt_forward takes: bf16 / fp16 acts, the padded layout, device-resident lengths (no host read,
+ * capturable), and a restricting p->alignment -- the expectation is then under the restricted distribution.
+ * Checked on the host before any device call (RNNT_STATUS_INVALID_VALUE): everything mrnnt_forward checks, a NULL or
+ * too small workspace, NULL grads. Workspace: mrnnt_expect_workspace_size(p) bytes (>= mrnnt_workspace_size: the loss's
+ * arrays, then A, Bk and R). Asynchronous on `stream`. The recursion launch counts under [2] of mrnnt_profile_read, the
+ * gradient under [3]. */
+RNNTStatus mrnnt_expect_workspace_size(const mrnnt_problem *p, size_t *bytes);
+RNNTStatus mrnnt_expect_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                const float *blank_cost_dev, const float *label_cost_dev, float *expected_dev,
+                                float *costs_dev, int with_grad, hipStream_t stream);
+RNNTStatus mrnnt_expect_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                 const float *blank_cost_dev, const float *label_cost_dev,
+                                 const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
+                                 hipStream_t stream);
+RNNTStatus mrnnt_expect_backward_tracked(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                         const float *blank_cost_dev, const float *label_cost_dev,
+                                         const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
+                                         unsigned char *row_state, int64_t row_state_len, hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -349,6 +402,16 @@ RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *workspace, size_
 RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, const int *alignments,
                                    int num_paths, int64_t path_stride, const float *weights, float *grads,
                                    int num_threads);
+
+/* mrnnt_expect_workspace_size / mrnnt_expect_forward / mrnnt_expect_backward for the host implementation: host buffers
+ * (fp32 acts), the same formulas, masks, exact zeros, NaN rule and host checks, in fp64 with the library exp. */
+RNNTStatus mrnnt_cpu_expect_workspace_size(const mrnnt_problem *p, size_t *bytes);
+RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                    const float *blank_cost, const float *label_cost, float *expected, float *costs,
+                                    int with_grad, int num_threads);
+RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                     const float *blank_cost, const float *label_cost, const float *grad_expected,
+                                     const float *grad_costs, float *grads, int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the
@@ -550,7 +613,8 @@ int mrnnt_version(void);
  *   [5] joint forward, [6] joint backward, [7] joint reduce, [8] chase launch (log-softmax + alpha/beta),
  *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch, mrnnt_posteriors and mrnnt_sample count under [2],
  *   and so do the walk, score and coefficient launches of mrnnt_path_forward / mrnnt_path_backward (their log-softmax
- *   under [1], their gradient under [3]). */
+ *   under [1], their gradient under [3]) and the recursion launch of mrnnt_expect_forward (the gradient of
+ *   mrnnt_expect_backward under [3]). */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

@@ -336,6 +336,105 @@ RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t 
     return RNNT_STATUS_SUCCESS;
 }
 
+}  // extern "C"
+
+namespace {
+
+// mrnnt_expect_*: the loss's plan (a restricting alignment included), then the expectation state A / Bk / R.
+struct ExpectPlan {
+    Plan pl;
+    size_t off_A = 0, off_Bk = 0, off_R = 0, total = 0;
+};
+
+RNNTStatus make_expect_plan(const mrnnt_problem *p, ExpectPlan *ep) {
+    const RNNTStatus st = make_plan(p, &ep->pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = ep->pl;
+    size_t o = pl.total;
+    ep->off_A = o;
+    o = align_up(o + sizeof(double) * (size_t)pl.N);
+    ep->off_Bk = o;
+    o = align_up(o + sizeof(double) * (size_t)pl.N);
+    ep->off_R = o;
+    o = align_up(o + sizeof(double) * (size_t)pl.B);
+    ep->total = o;
+    return RNNT_STATUS_SUCCESS;
+}
+
+void expect_dev(const ExpectPlan &ep, void *ws, const float *blank_cost_dev, const float *label_cost_dev, DevProblem *d) {
+    d->ex_A = carve<double>(ws, ep.off_A);
+    d->ex_Bk = carve<double>(ws, ep.off_Bk);
+    d->ex_R = carve<double>(ws, ep.off_R);
+    d->ex_wb = blank_cost_dev;
+    d->ex_we = label_cost_dev;
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_expect_workspace_size(const mrnnt_problem *p, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    ExpectPlan ep;
+    const RNNTStatus st = make_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = ep.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                const float *label_cost_dev, float *expected_dev, float *costs_dev, int with_grad,
+                                hipStream_t stream) {
+    ExpectPlan ep;
+    RNNTStatus st = make_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    // the loss's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
+    if ((st = mrnnt_forward(p, ws, ws_bytes, costs_dev, with_grad ? 1 : 0, stream)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, ep.pl, ws);
+    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_expect(d, ep.pl.S_max, with_grad ? 1 : 0, expected_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "expectation recursion kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                 const float *label_cost_dev, const float *grad_expected_dev,
+                                 const float *grad_costs_dev, void *grads, hipStream_t stream) {
+    return mrnnt_expect_backward_tracked(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, grad_expected_dev,
+                                         grad_costs_dev, grads, nullptr, 0, stream);
+}
+
+RNNTStatus mrnnt_expect_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                         const float *label_cost_dev, const float *grad_expected_dev,
+                                         const float *grad_costs_dev, void *grads, unsigned char *row_state,
+                                         int64_t row_state_len, hipStream_t stream) {
+    ExpectPlan ep;
+    RNNTStatus st = make_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = ep.pl;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, pl, ws);
+    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
+    d.row_state = row_state;
+    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    d.ex_ge = grad_expected_dev;
+    d.ex_gc = grad_costs_dev;
+    d.col_mul = column_order(pl, 2);
+    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    hipError_t e = timed(K_GRAD, stream, [&] { return launch_expect_grad(d, pl.elem, grads, grid, stream); });
+    if (e != hipSuccess) return fail_hip(e, "expected-cost gradient kernel");
+    if (pl.pad_S1 != 0) {
+        e = launch_pad_zero(d, pl.elem, grads, stream);
+        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,
                              hipStream_t stream) {
     Plan pl;

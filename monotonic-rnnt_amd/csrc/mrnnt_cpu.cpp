@@ -922,6 +922,196 @@ RNNTStatus mrnnt_cpu_read_state(const mrnnt_problem *p, const void *ws, float *d
 
 }  // extern "C"
 
+// ---- mrnnt_cpu_expect_*: expected path costs and their logit gradient (the HIP path's mrnnt_expect.hip) -------------
+namespace {
+
+struct CpuExpectPlan {
+    CpuPlan pl;
+    size_t off_A = 0, off_Bk = 0, off_R = 0, total = 0;
+};
+
+RNNTStatus make_cpu_expect_plan(const mrnnt_problem *p, CpuExpectPlan *ep) {
+    const RNNTStatus st = make_cpu_plan(p, &ep->pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const CpuPlan &pl = ep->pl;
+    ep->off_A = pl.total;
+    ep->off_Bk = align_up(ep->off_A + sizeof(double) * (size_t)pl.N);
+    ep->off_R = align_up(ep->off_Bk + sizeof(double) * (size_t)pl.N);
+    ep->total = align_up(ep->off_R + sizeof(double) * (size_t)pl.B);
+    return RNNT_STATUS_SUCCESS;
+}
+
+// band(u): the states before frame u, 0 <= u <= T (the bounds of alpha_utt / beta_utt)
+inline void state_band(const Views &w, int64_t c0, int T, int S, int u, int &lo, int &hi) {
+    lo = std::max(u - (T - S), 0);
+    hi = std::min(u, S);
+    if (w.min_s && u > 0) {
+        lo = std::max(lo, w.min_s[c0 + u - 1]);
+        hi = std::min(hi, w.max_s[c0 + u - 1]);
+    }
+    if (u == 0) hi = 0;
+}
+
+// new = q * self + p * neighbour + c: the convex mix of the blank arc (log-weight x, cost cx) and the label arc (y, cy);
+// the smaller weight is e / (1 + e), the other one 1 minus it (they sum to exactly 1); both -inf: no path, all 0
+inline void arc_mix(double x, double y, double cx, double cy, double &q, double &pw, double &c) {
+    if (x == kNegInf && y == kNegInf) {
+        q = pw = c = 0.0;
+        return;
+    }
+    const double e = std::exp(-std::fabs(x - y));
+    const double wl = e / (1.0 + e);
+    const bool ybig = y > x;
+    pw = ybig ? 1.0 - wl : wl;
+    q = ybig ? wl : 1.0 - wl;
+    c = (q != 0.0 ? q * cx : 0.0) + (pw != 0.0 ? pw * cy : 0.0);
+}
+
+// A(t, .) for t = 0 .. T-1 (bwd: Bk(t, .) for t = T-1 .. 0) of one utterance; returns A(T-1, S) (bwd: Bk(0, 0))
+double expect_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, double *out, const float *wb,
+                  const float *we, int b, bool bwd) {
+    const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+    const int64_t r0 = pl.row_off[b], c0 = pl.col_off[b];
+    const double *state = (bwd ? w.beta : w.alpha) + r0;
+    double *O = out + r0;
+    const int first = bwd ? T - 1 : 0;
+    for (int i = 0; i < T; ++i) {
+        const int t = bwd ? T - 1 - i : i;
+        int lo_c, hi_c, lo_o, hi_o;
+        state_band(w, c0, T, S, bwd ? t : t + 1, lo_c, hi_c);
+        state_band(w, c0, T, S, bwd ? t + 1 : t, lo_o, hi_o);
+        const bool edge = t == first;
+        const int to = bwd ? std::min(t + 1, T - 1) : std::max(t - 1, 0);  // the other end's frame (not read at the edge)
+        const double *st = state + (int64_t)to * W;
+        const double *prev = O + (int64_t)to * W;
+        const double *pb = w.lpb + r0 + (int64_t)t * W, *pe = w.lpe + r0 + (int64_t)t * W;
+        const int64_t a0 = acts_row(pl, b, t, W);
+        double *o = O + (int64_t)t * W;
+        for (int s = 0; s < W; ++s) {
+            if (s < lo_c || s > hi_c) {
+                o[s] = 0.0;
+                continue;
+            }
+            const int sn = bwd ? s + 1 : s - 1, se = bwd ? s : s - 1;
+            const bool okx = s >= lo_o && s <= hi_o;
+            const bool oky = sn >= lo_o && sn <= hi_o && (bwd ? s < S : s > 0);
+            const double x = okx ? (edge ? 0.0 : st[s]) + pb[s] : kNegInf;
+            const double y = oky ? (edge ? 0.0 : st[sn]) + pe[se] : kNegInf;
+            double q, pw, c;
+            arc_mix(x, y, (okx && wb) ? (double)wb[a0 + s] : 0.0, (oky && we) ? (double)we[a0 + se] : 0.0, q, pw, c);
+            o[s] = q * (edge ? 0.0 : prev[s]) + pw * ((edge || !oky) ? 0.0 : prev[sn]) + c;
+        }
+    }
+    return bwd ? O[0] : O[(int64_t)(T - 1) * W + S];
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_cpu_expect_workspace_size(const mrnnt_problem *p, size_t *bytes) {
+    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    CpuExpectPlan ep;
+    const RNNTStatus st = make_cpu_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = ep.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                    const float *label_cost, float *expected, float *costs, int with_grad,
+                                    int num_threads) {
+    CpuExpectPlan ep;
+    RNNTStatus st = make_cpu_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const CpuPlan &pl = ep.pl;
+    if (!ws || ws_bytes < ep.total)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(ep.total) + " bytes");
+    if ((st = mrnnt_cpu_forward(p, ws, ws_bytes, costs, with_grad ? 1 : 0, num_threads)) != RNNT_STATUS_SUCCESS) return st;
+    const Views w = views(pl, ws);
+    char *base = static_cast<char *>(ws);
+    double *A = reinterpret_cast<double *>(base + ep.off_A), *Bk = reinterpret_cast<double *>(base + ep.off_Bk);
+    double *R = reinterpret_cast<double *>(base + ep.off_R);
+    const int nt = threads_of(num_threads);
+    const int dirs = with_grad ? 2 : 1;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+    for (int i = 0; i < pl.B * dirs; ++i) {
+        const int b = i / dirs;
+        if (i % dirs == 0) {
+            R[b] = expect_utt(p, pl, w, A, blank_cost, label_cost, b, false);
+            if (expected) expected[b] = std::isfinite(w.ll[b]) ? (float)R[b] : std::numeric_limits<float>::quiet_NaN();
+        } else {
+            expect_utt(p, pl, w, Bk, blank_cost, label_cost, b, true);
+        }
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                     const float *label_cost, const float *grad_expected, const float *grad_costs,
+                                     float *grads, int num_threads) {
+    CpuExpectPlan ep;
+    RNNTStatus st = make_cpu_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const CpuPlan &pl = ep.pl;
+    if (!p->acts) return set_error(RNNT_STATUS_INVALID_VALUE, "acts is null");
+    if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
+    if (!grads) return set_error(RNNT_STATUS_INVALID_VALUE, "grads is null");
+    if (!ws || ws_bytes < ep.total)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(ep.total) + " bytes");
+    const Views w = views(pl, ws);
+    const char *base = static_cast<const char *>(ws);
+    const double *A = reinterpret_cast<const double *>(base + ep.off_A);
+    const double *Bk = reinterpret_cast<const double *>(base + ep.off_Bk);
+    const double *Rv = reinterpret_cast<const double *>(base + ep.off_R);
+    const int nt = threads_of(num_threads);
+    const int V = pl.V;
+    const float *acts = static_cast<const float *>(p->acts);
+#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
+    for (int64_t c = 0; c < pl.cols; ++c) {
+        const int b = col_utt(pl, c);
+        const int t = (int)(c - pl.col_off[b]);
+        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
+        const double ll = w.ll[b], R = Rv[b];
+        const bool fin = std::isfinite(ll), last = t == T - 1;
+        const double ge = grad_expected ? (double)grad_expected[b] : 0.0, gc = grad_costs ? (double)grad_costs[b] : 0.0;
+        const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
+        for (int s = 0; s < W; ++s) {
+            float *g = grads + (a0 + s) * V;
+            const int64_t r = r0 + s;
+            double Wb = 0.0, We = 0.0;
+            if (fin && s >= lo && s <= hi) {
+                const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : w.alpha[r - W];
+                const double bs = am - ll;
+                if (!(bs + w.beta[r] < mrnnt::kDeadLogOcc)) {
+                    const double b1 = last ? (s == S ? 0.0 : kNegInf) : w.beta[r + W];
+                    const double b2 = (s == S) ? kNegInf : (last ? (s + 1 == S ? 0.0 : kNegInf) : w.beta[r + W + 1]);
+                    const double pb = std::exp(w.lpb[r] + bs + b1), pe = (s < S) ? std::exp(w.lpe[r] + bs + b2) : 0.0;
+                    const double ap = (t == 0) ? 0.0 : A[r - W];
+                    if (pb != 0.0)
+                        Wb = pb * (gc - ge * (ap + (blank_cost ? (double)blank_cost[a0 + s] : 0.0) + (last ? 0.0 : Bk[r + W]) - R));
+                    if (pe != 0.0)
+                        We = pe * (gc - ge * (ap + (label_cost ? (double)label_cost[a0 + s] : 0.0) +
+                                              (last ? 0.0 : Bk[r + W + 1]) - R));
+                }
+            }
+            if ((float)Wb == 0.0f && (float)We == 0.0f) {  // exact zeros (NaN: no finite ll), acts not read
+                std::fill(g, g + V, fin ? 0.0f : std::numeric_limits<float>::quiet_NaN());
+                continue;
+            }
+            grad_row(acts + (a0 + s) * V, g, V, w.den[r], (float)(Wb + We));
+            g[p->blank] -= (float)Wb;
+            if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)We;
+        }
+    }
+    zero_padding_rows(p, pl, grads, V, nt);
+    return RNNT_STATUS_SUCCESS;
+}
+
+}  // extern "C"
+
 // =================================================================================================
 // reference-shaped C++ surface (reference include/cpu_workspace_manager.h, include/cpu_rnnt.h)
 

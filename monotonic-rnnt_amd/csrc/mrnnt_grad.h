@@ -1,5 +1,6 @@
 // mrnnt_grad.h -- the dense logit-gradient streamers and their launch ladder, over a compile-time row policy P: the
-// loss gradient (LossRows, mrnnt_grad.hip) and the path-score gradient (PathRows, mrnnt_path.hip). P supplies
+// loss gradient (LossRows, mrnnt_grad.hip), the path-score gradient (PathRows, mrnnt_path.hip) and the expected-cost
+// gradient (ExpectRows, mrnnt_expect.hip). P supplies
 //   Col, column()   what a lattice column sets up once: its band of rows with a gradient; zero(): the other rows' value
 //   Slot, stage()   a row's coefficients as they are staged in LDS, two buffers of 256 slots (a dead slot: the row is
 //                   stored as zero()), live(); skip() / skipped(): a dead slot whose row already holds zero() (row state)
@@ -162,6 +163,53 @@ __global__ __launch_bounds__(256) void grad_scalar_kernel(DevProblem p, const fl
         }
     }
 }
+
+// The slot and the formula of the policies whose rows carry two signed arc weights Wb / We in place of the loss's
+// occupancy and posteriors (PathRows, mrnnt_path.hip; ExpectRows, mrnnt_expect.hip):
+//   g[v] = (Wb + We) softmax(z_r)[v] - [v == blank] Wb - [v == label(s)] We;  no upstream scale (it is in the weights).
+// The policy adds Col / column() / zero() / stage() / row() / launch_u().
+struct WeightRows {
+    struct Slot {
+        float c2;    // den * log2(e)
+        float wocc;  // Wb + We (signed; 0 on cancellation)
+        float cb;    // Wb
+        float ce;    // We
+        int lab;     // label(s), -1 for s == S / label == blank / out of range; kDeadRow: the row is stored as zeros
+    };
+    typedef Slot Coef;
+    static __device__ __forceinline__ bool live(const Slot &c) { return c.lab > kDeadRow; }
+    static __device__ __forceinline__ void skip(Slot &c) { c.lab = kSkipRow; }
+    static __device__ __forceinline__ bool skipped(const Slot &c) { return c.lab == kSkipRow; }
+    static __device__ __forceinline__ const Coef &coef(const Slot &c) { return c; }
+    // label(s) as the slot holds it
+    static __device__ __forceinline__ int slot_label(const DevProblem &p, int S, int s, const int *lab_b) {
+        const int lab = (s < S) ? lab_b[s] : -1;
+        return (lab == p.blank || (unsigned)lab >= (unsigned)p.V) ? -1 : lab;
+    }
+
+    template <class IO>
+    static __device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const Slot &rc, int j, int blank,
+                                                              float) {
+        constexpr int E = IO::E;
+        float x[E];
+        IO::unpack(xv, x);
+        const int v0 = j * E;
+        const int db = blank - v0;
+        const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const float g = rc.wocc * fast_exp2(fmaf(x[i], kLog2e, rc.c2));
+            x[i] = g - ((db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f));
+        }
+        return IO::pack(x);
+    }
+    static __device__ __forceinline__ float grad(float z, int v, const Slot &rc, int blank, float) {
+        float g = rc.wocc * fast_exp2(fmaf(z, kLog2e, rc.c2));
+        if (v == blank) g -= rc.cb;
+        else if (v == rc.lab) g -= rc.ce;
+        return g;
+    }
+};
 
 // A launch of a kernel that does not keep the row state (every kernel but the staged one): the covered rows become
 // "unknown" before it runs, in stream order. (A failed memset is reported by the launch's hipGetLastError.)

@@ -73,6 +73,13 @@ struct DevProblem {
     // mrnnt_backward_tracked / mrnnt_path_backward_tracked: one byte per row of grads -- 0 unknown, 1 the row is all
     // +0.0, 2 all -0.0 -- read and rewritten by the gradient launch (mrnnt_grad.h); nullptr: every row is written
     unsigned char *row_state = nullptr;
+    // mrnnt_expect_* (mrnnt_expect.hip): the expectation state of the call's workspace -- A(t, s) after frame t and
+    // Bk(t, s) before frame t ([N] fp64, 0 on cells no path reaches), R[b] = the expected cost -- the caller's two cost
+    // arrays (one fp32 per acts row in acts' row layout; nullptr = all zeros) and the two upstream gradients of the
+    // backward ([B]; nullptr = 0). Read by the expectation launch and by ExpectRows only.
+    double *ex_A = nullptr, *ex_Bk = nullptr, *ex_R = nullptr;
+    const float *ex_wb = nullptr, *ex_we = nullptr;
+    const float *ex_ge = nullptr, *ex_gc = nullptr;
 };
 
 // rows of the caller's grads buffer a gradient launch covers (host bound)
@@ -317,6 +324,13 @@ hipError_t launch_path_walk(const DevProblem &p, const PathArgs &a, int T_bound,
 hipError_t launch_path_score(const DevProblem &p, const PathArgs &a, hipStream_t stream);
 hipError_t launch_path_coef(const DevProblem &p, const PathArgs &a, int T_bound, hipStream_t stream);
 hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
+
+// mrnnt_expect_forward / mrnnt_expect_backward (mrnnt_expect.hip): the first-order expectation recursion over the
+// state of a forward (p.ex_A forward in time and, with_bk, p.ex_Bk backward, one workgroup per utterance and
+// direction; p.ex_R and expected[b] = fp32(R), NaN for a non-finite ll; expected may be null), and the dense gradient
+// of g_e . expected + g_c . costs over the row policy ExpectRows.
+hipError_t launch_expect(const DevProblem &p, int S_max, int with_bk, float *expected, hipStream_t stream);
+hipError_t launch_expect_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
 
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that

@@ -186,7 +186,8 @@ __global__ __launch_bounds__(256) void path_coef_kernel(DevProblem p, PathArgs a
 
 // The path scores' rows for the shared streamers (mrnnt_grad.h): band = the hull of the column, a row's staged
 // coefficients from Wb / We / den, the other rows plain zeros; no upstream scale (the weights are in Wb / We).
-struct PathRows {
+// Slot, formula and scalar twin: WeightRows (mrnnt_grad.h).
+struct PathRows : WeightRows {
     struct Col {
         int lo, hi;
     };
@@ -195,14 +196,6 @@ struct PathRows {
     }
     static __device__ __forceinline__ float zero(const Col &, float) { return 0.0f; }
 
-    struct Slot {
-        float c2;    // den * log2(e)
-        float wocc;  // Wb + We (signed; 0 on cancellation)
-        float cb;    // Wb
-        float ce;    // We
-        int lab;     // label(s), -1 for s == S / label == blank / out of range; kDeadRow: the row is stored as zeros
-    };
-    typedef Slot Coef;
     // (as the loss's row_coef: nothing of the row is read before it is known to be in the hull)
     static __device__ __forceinline__ Slot stage(const DevProblem &p, const Col &col, int, int S, int s, int64_t rowc,
                                                  const int *lab_b) {
@@ -215,41 +208,13 @@ struct PathRows {
         c.wocc = (float)(wb + we);
         c.cb = (float)wb;
         c.ce = (float)we;
-        const int lab = (s < S) ? lab_b[s] : -1;
-        c.lab = (lab == p.blank || (unsigned)lab >= (unsigned)p.V) ? -1 : lab;
+        c.lab = slot_label(p, S, s, lab_b);
         return c;
     }
     static __device__ __forceinline__ bool row(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
                                                const int *lab_b, Coef &c) {
         c = stage(p, col, t, S, s, rowc, lab_b);
         return live(c);
-    }
-    static __device__ __forceinline__ bool live(const Slot &c) { return c.lab > kDeadRow; }
-    static __device__ __forceinline__ void skip(Slot &c) { c.lab = kSkipRow; }
-    static __device__ __forceinline__ bool skipped(const Slot &c) { return c.lab == kSkipRow; }
-    static __device__ __forceinline__ const Coef &coef(const Slot &c) { return c; }
-
-    template <class IO>
-    static __device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const Slot &rc, int j, int blank,
-                                                              float) {
-        constexpr int E = IO::E;
-        float x[E];
-        IO::unpack(xv, x);
-        const int v0 = j * E;
-        const int db = blank - v0;
-        const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
-#pragma unroll
-        for (int i = 0; i < E; ++i) {
-            const float g = rc.wocc * fast_exp2(fmaf(x[i], kLog2e, rc.c2));
-            x[i] = g - ((db == i ? rc.cb : 0.0f) + (de == i ? rc.ce : 0.0f));
-        }
-        return IO::pack(x);
-    }
-    static __device__ __forceinline__ float grad(float z, int v, const Slot &rc, int blank, float) {
-        float g = rc.wocc * fast_exp2(fmaf(z, kLog2e, rc.c2));
-        if (v == blank) g -= rc.cb;
-        else if (v == rc.lab) g -= rc.ce;
-        return g;
     }
 
     // few rows are read (at most B K T of them): the loads keep the default policy; the stores are the pass

@@ -3,12 +3,14 @@ from .monotonic_rnnt_joint import (MonotonicRNNTJointFunction, MonotonicRNNTJoin
                                    monotonic_rnnt_joint_align, monotonic_rnnt_joint_loss,
                                    monotonic_rnnt_joint_path_loss, monotonic_rnnt_joint_posteriors,
                                    monotonic_rnnt_joint_sample)
-from .monotonic_rnnt_op import (MonotonicRNNTFunction, MonotonicRNNTLoss, MonotonicRNNTPathFunction,
-                                monotonic_rnnt_align, monotonic_rnnt_cpp, monotonic_rnnt_loss, monotonic_rnnt_path_loss,
+from .monotonic_rnnt_op import (MonotonicRNNTExpectedCostFunction, MonotonicRNNTFunction, MonotonicRNNTLoss,
+                                MonotonicRNNTPathFunction, monotonic_rnnt_align, monotonic_rnnt_cpp,
+                                monotonic_rnnt_expected_cost, monotonic_rnnt_loss, monotonic_rnnt_path_loss,
                                 monotonic_rnnt_posteriors, monotonic_rnnt_sample)
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp",
            "MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_align",
            "monotonic_rnnt_posteriors", "monotonic_rnnt_joint_align", "monotonic_rnnt_joint_posteriors",
            "monotonic_rnnt_sample", "monotonic_rnnt_joint_sample", "MonotonicRNNTPathFunction",
-           "monotonic_rnnt_path_loss", "MonotonicRNNTJointPathFunction", "monotonic_rnnt_joint_path_loss"]
+           "monotonic_rnnt_path_loss", "MonotonicRNNTJointPathFunction", "monotonic_rnnt_joint_path_loss",
+           "MonotonicRNNTExpectedCostFunction", "monotonic_rnnt_expected_cost"]

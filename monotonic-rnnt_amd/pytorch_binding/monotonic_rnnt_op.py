@@ -268,13 +268,14 @@ class _Prepared:
         self.problem = p
         self.device = dev
 
-    def workspace(self, num_paths: int = 0) -> torch.Tensor:
-        """The call's workspace; num_paths > 0: the one of monotonic_rnnt_path_loss for that many paths."""
+    def workspace(self, num_paths: int = 0, expect: bool = False) -> torch.Tensor:
+        """The call's workspace; num_paths > 0: the one of monotonic_rnnt_path_loss for that many paths; expect: the
+        one of monotonic_rnnt_expected_cost."""
         p = self.problem
         # the plan also depends on V and the acts element type (whether the chase launch applies, and so whether the
         # workspace holds its ready flags) and on the device (its CU count bounds the chase)
         key = (self.on_gpu, self.alignment is not None, _L.load(), p.V, p.acts_dtype, str(self.device), p.pad_T,
-               p.pad_S1, num_paths)
+               p.pad_S1, -1 if expect else num_paths)
         if self.dyn:  # sized from bounds: the shapes of acts and labels
             key = key + (p.B, p.num_rows, p.label_stride)
             cache = _DYN_WS
@@ -283,7 +284,11 @@ class _Prepared:
         n = cache.get(key)
         if n is None:
             c = ctypes.c_size_t(0)
-            if num_paths > 0:
+            if expect:
+                size = _L.load().mrnnt_expect_workspace_size if self.on_gpu else _L.load().mrnnt_cpu_expect_workspace_size
+                with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
+                    _L.check(size(ctypes.byref(self.problem), ctypes.byref(c)), "expect_workspace_size")
+            elif num_paths > 0:
                 size = _L.load().mrnnt_path_workspace_size if self.on_gpu else _L.load().mrnnt_cpu_path_workspace_size
                 with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
                     _L.check(size(ctypes.byref(self.problem), num_paths, ctypes.byref(c)), "path_workspace_size")
@@ -642,6 +647,104 @@ def monotonic_rnnt_path_loss(acts: torch.Tensor, labels: torch.Tensor, input_len
     return MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments, blank_label)
 
 
+def _cost_array(x: Optional[torch.Tensor], prep: _Prepared, what: str) -> Optional[torch.Tensor]:
+    """A per-arc cost array as the library takes it: float32, one value per row of acts, on acts' device."""
+    if x is None:
+        return None
+    rows = tuple(prep.acts.shape[:-1])
+    if tuple(x.shape) != rows:
+        raise RuntimeError(f"monotonic_rnnt_expected_cost: {what} must have one value per row of acts, shape "
+                           f"{rows}, got {tuple(x.shape)}")
+    return x.detach().to(prep.device, torch.float32).contiguous()
+
+
+def _upstream(g: Optional[torch.Tensor], prep: _Prepared) -> Optional[torch.Tensor]:
+    return None if g is None else g.detach().to(prep.device, torch.float32).contiguous()
+
+
+class MonotonicRNNTExpectedCostFunction(torch.autograd.Function):
+    """Expected path costs and the loss with their logit gradient (mrnnt_expect_forward / mrnnt_expect_backward and the
+    mrnnt_cpu_expect_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, blank_costs,
+    label_costs, alignment=None, max_distance_from_alignment=0, blank_label=0) -> (expected [B], costs [B]). The two
+    upstream gradients go into one backward call that writes one gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                label_lengths: torch.Tensor, blank_costs: Optional[torch.Tensor] = None,
+                label_costs: Optional[torch.Tensor] = None, alignment: Optional[torch.Tensor] = None,
+                max_distance_from_alignment: int = 0, blank_label: int = 0):
+        prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
+                         blank_label)
+        wb = _cost_array(blank_costs, prep, "blank_costs")
+        we = _cost_array(label_costs, prep, "label_costs")
+        need_grad = bool(ctx.needs_input_grad[0])
+        ws = prep.workspace(expect=True)
+        B, dev = prep.problem.B, prep.device
+        expected = torch.empty(B, dtype=torch.float32, device=dev)
+        costs = torch.empty(B, dtype=torch.float32, device=dev)
+        _call(prep, "expect_forward", _ptr(ws), ws.numel(), _ptr(wb), _ptr(we), _ptr(expected), _ptr(costs),
+              1 if need_grad else 0, pending=True)
+        if need_grad:
+            # acts is re-read by the gradient kernel; the workspace holds the loss's state and A / Bk / R
+            ctx.save_for_backward(acts, ws)
+            ctx.prep, ctx.wb, ctx.we = prep, wb, we
+        return expected, costs
+
+    @staticmethod
+    def backward(ctx, grad_expected, grad_costs):
+        _, ws = ctx.saved_tensors
+        prep = ctx.prep
+        ge, gc = _upstream(grad_expected, prep), _upstream(grad_costs, prep)
+        # the tracked, placement-probed buffer of the loss's backward (_grads_placement)
+        grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
+        if ticket is not None:
+            _call(prep, "expect_backward_tracked", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
+                  _ptr(grads), _ptr(ticket.state), ticket.state.numel(), lengths=False)
+            ticket.commit()
+        else:
+            _call(prep, "expect_backward", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
+                  _ptr(grads), lengths=False)
+        return grads, None, None, None, None, None, None, None, None
+
+
+def monotonic_rnnt_expected_cost(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                                 label_lengths: torch.Tensor, blank_costs: Optional[torch.Tensor] = None,
+                                 label_costs: Optional[torch.Tensor] = None,
+                                 alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
+                                 blank_label: int = 0):
+    """The exact expectation, under the path posterior p(path | labels, acts) of the lattice the loss sums over, of a
+    cost that adds up over the arcs of a path -- and the loss of the same inputs -- both differentiable with respect to
+    acts (the first-order expectation semiring: one more recursion over the forward's state, no sampling):
+
+        expected[b] = sum_path p(path) sum_t cost(arc_t)      (= sum_rows blank_post * blank_costs + label_post * label_costs
+                                                                 with monotonic_rnnt_posteriors of the same inputs)
+
+    Emission time gives the expected latency streaming models are regularised with, blank_costs = 1 the expected blank
+    count, a per-arc risk a minimum-risk objective:
+
+        t = torch.arange(T_max).view(1, -1, 1).expand(B, T_max, S_max + 1)           # padded 4-D acts
+        latency, costs = monotonic_rnnt_expected_cost(acts, labels, T, S, label_costs=t.float())
+        (costs + 0.01 * latency).sum().backward()                                     # one gradient pass, one buffer
+
+    Args: acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label as
+    monotonic_rnnt_loss (CPU or GPU tensors; GPU: also bfloat16 / float16 acts, the padded 4-D layout, GPU-resident
+    lengths without a host read). With `alignment` the expectation is under the restricted distribution.
+        blank_costs, label_costs: float tensors of shape acts.shape[:-1] -- one value per lattice row (b, t, s), the
+                    layout of monotonic_rnnt_posteriors' blank / label -- the cost of the blank arc / the label arc out
+                    of that row; either may be None (all zeros). Signed costs are fine. label_costs at s = S_b and
+                    anything at padding rows is ignored.
+    Returns (expected, costs), both float32 [B] on acts.device; costs is monotonic_rnnt_loss's (bit-identical).
+    The backward of any function of the two is ONE call that writes ONE gradient buffer (the loss's own gradient folded
+    into the same dense pass). The cost arrays are not differentiated: their gradient is the arc posteriors
+    (monotonic_rnnt_posteriors). Rows outside the band, unreachable rows and rows whose coefficients underflow have an
+    exactly zero gradient and are not read. An utterance without a finite cost has a NaN expected value and NaN gradient
+    rows; the others are unaffected. Results are bitwise reproducible and do not depend on the other utterances.
+    GPU-resident lengths that fail validation make every value NaN and surface through check_lengths() as for the
+    loss."""
+    return MonotonicRNNTExpectedCostFunction.apply(acts, labels, input_lengths, label_lengths, blank_costs, label_costs,
+                                                   alignment, max_distance_from_alignment, blank_label)
+
+
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
@@ -713,4 +816,5 @@ monotonic_rnnt_cpp = _Ext()
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
            "monotonic_rnnt_align", "monotonic_rnnt_posteriors", "monotonic_rnnt_sample",
-           "MonotonicRNNTPathFunction", "monotonic_rnnt_path_loss"]
+           "MonotonicRNNTPathFunction", "monotonic_rnnt_path_loss", "MonotonicRNNTExpectedCostFunction",
+           "monotonic_rnnt_expected_cost"]
