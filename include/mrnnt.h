@@ -599,6 +599,53 @@ RNNTStatus mrnnt_joint_path_rows(const mrnnt_joint_problem *p, void *workspace, 
 RNNTStatus mrnnt_joint_path_backward(const mrnnt_joint_problem *p, void *workspace, int64_t n_rows, void *G, void *Hact,
                                      int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream);
 
+/* mrnnt_expect_forward / mrnnt_expect_backward for the fused joint (an addition to version 13: MRNNT_VERSION and both
+ * structs are unchanged, so callers that may meet an older build of version 13 probe for the symbol
+ * mrnnt_joint_expect_forward): the exact expectation of an arc-additive cost under the logits the joint never stores,
+ * and the gradients of sum_b g_e[b] expected[b] + g_c[b] costs[b] for enc, pred, weight and bias through the joint's
+ * own backward chain -- ONE set of row coefficients over ONE row list, whatever the two upstream gradients are. The
+ * contract is that of mrnnt_expect_* above (A, Bk, R, cb, ce as defined there), stated for the joint:
+ *   blank_cost_dev / label_cost_dev: wb / we, fp32 [B, grid_T, grid_S1], row (b, t, s) at (b*grid_T + t)*grid_S1 + s
+ *       -- the grid mrnnt_joint_posteriors writes blank_post / label_post on; grid_T >= max T_b, grid_S1 >= max S_b + 1.
+ *       Either may be NULL (all zeros; with both NULL the grid is not looked at). we at s = S_b, and anything at
+ *       t >= T_b or s > S_b, never enters a result. The cost arrays are not differentiated.
+ *   Wb = g_c blank_post - g_e cb,   We = g_c label_post - g_e ce     (fp64, the function of mrnnt_expect_backward)
+ *   g[r, v] = (Wb + We) softmax(z_r)[v] - [v == blank] Wb - [v == label(s)] We     (mrnnt_joint_path_backward's formula)
+ *   A row whose two fp32 coefficients are both zero is not in the backward's row list. An utterance whose ll is not
+ *   finite has expected[b] NaN and every row of its monotonic band listed with NaN coefficients (as mrnnt_joint_backward
+ *   treats it); the other utterances' expected and costs are bit-identical to a call without it. With p->alignment the
+ *   expectation is under the restricted distribution. Every sum has a fixed order, no atomics: expected, costs and all
+ *   four gradients are bitwise reproducible.
+ * Calls, on one workspace of mrnnt_joint_expect_workspace_size(p) bytes:
+ *   mrnnt_joint_expect_forward: mrnnt_joint_forward(with_beta = with_grad) (costs_dev: the loss, bit for bit), then
+ *       the expectation recursion of mrnnt_expect_forward on the joint's packed lattice; expected_dev[b] = fp32(R)
+ *       (either output may be NULL).
+ *   mrnnt_joint_expect_rows (after it with with_grad = 1; the same cost arrays and grid): grad_expected_dev /
+ *       grad_costs_dev are fp32 [B], either may be NULL = 0 for that term; one coefficient launch writes Wb / We of
+ *       every row of the monotonic band (exact 0.0 for a dead row), then the list of the expect-live rows (Wb != 0 ||
+ *       We != 0, column order, s ascending) with its count in *count_dev (device uint64). mrnnt_joint_row_bound is the
+ *       host-known bound on that count.
+ *   mrnnt_joint_expect_backward: mrnnt_joint_path_backward's gradient pass over that list, reading Wb / We from the two
+ *       arrays. G, Hact, bt_idx, bs_idx, p->hact_ld, p->dbias and p->live_count_dev as there.
+ *   Then mrnnt_joint_dpre / mrnnt_joint_reduce / mrnnt_joint_reduce_pre exactly as after mrnnt_joint_backward: the
+ *       workspace is laid out as mrnnt_joint_workspace_size's of the same problem FOLLOWED by A, Bk (fp64 [N]), R (fp64
+ *       [B]) and Wb, We (fp64 [N]), so those entry points work on it unchanged.
+ * Checked on the host before any device call (RNNT_STATUS_INVALID_VALUE): everything mrnnt_joint_forward checks; a
+ * grid smaller than [max T, max S + 1] when either cost array is given; a NULL or too small workspace; a NULL
+ * count_dev. Asynchronous on `stream`, no host read. The recursion and coefficient launches count under [2] of
+ * mrnnt_profile_read, the joint pass under [5], the gradient pass under [6]. */
+RNNTStatus mrnnt_joint_expect_workspace_size(const mrnnt_joint_problem *p, size_t *bytes);
+RNNTStatus mrnnt_joint_expect_forward(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                      const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
+                                      int64_t grid_S1, float *expected_dev, float *costs_dev, int with_grad,
+                                      hipStream_t stream);
+RNNTStatus mrnnt_joint_expect_rows(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                   const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
+                                   int64_t grid_S1, const float *grad_expected_dev, const float *grad_costs_dev,
+                                   unsigned long long *count_dev, hipStream_t stream);
+RNNTStatus mrnnt_joint_expect_backward(const mrnnt_joint_problem *p, void *workspace, int64_t n_rows, void *G,
+                                       void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream);
+
 /* Nontemporal zero fill of `bytes` (a multiple of 16) at `dst` (16-byte aligned device memory), in the gradient
  * pass's store pattern. The Python surface times it once over a newly allocated large grads buffer to pick a
  * fast-writing physical placement; also usable as a plain fill. Asynchronous on `stream`. */
@@ -614,7 +661,7 @@ int mrnnt_version(void);
  *   [9] joint dpre GEMM (version 10). mrnnt_align's Viterbi launch, mrnnt_posteriors and mrnnt_sample count under [2],
  *   and so do the walk, score and coefficient launches of mrnnt_path_forward / mrnnt_path_backward (their log-softmax
  *   under [1], their gradient under [3]) and the recursion launch of mrnnt_expect_forward (the gradient of
- *   mrnnt_expect_backward under [3]). */
+ *   mrnnt_expect_backward under [3]) and the recursion and coefficient launches of mrnnt_joint_expect_*. */
 void mrnnt_profile_enable(int enable);
 int mrnnt_profile_read(double *total_ms, int64_t *launches, int n);
 

@@ -35,6 +35,9 @@
 // The gradient: the shared streamers of mrnnt_grad.h over ExpectRows, the slot and the formula those of the path
 // scores (WeightRows) with
 //   Wb = g_c blank_post - g_e cb,   We = g_c label_post - g_e ce     (the deviation A + w + Bk - R first, in fp64).
+// The fused joint (mrnnt_joint_expect_*) has no dense gradient: expect_coef_kernel writes the same Wb / We -- one
+// function, expect_weights, forms them for both -- of every in-band row into two arrays, from which mrnnt_joint.hip
+// lists the rows that have any and runs its MFMA gradient pass with the path scores' coefficients.
 #include <algorithm>
 
 #include "mrnnt_dp.h"
@@ -214,6 +217,144 @@ struct ExpectLaunch {  // launch_by_width's go<K, NW>()
 
 // ---- gradient ------------------------------------------------------------------------------------------------------
 
+// The two weights of an in-band row (t, s) of g_e . expected + g_c . costs, in fp64 -- shared by the dense gradient
+// (ExpectRows::stage) and the fused joint's coefficient launch (expect_coef_kernel):
+//   Wb = blank_post (g_c - g_e (A(t-1, s) + wb + Bk(t+1, s)   - R))
+//   We = label_post (g_c - g_e (A(t-1, s) + we + Bk(t+1, s+1) - R))      (0 at s = S: label_arc false)
+// the posteriors as row_coef forms them, the deviation from the mean in fp64 first; {0, 0} for a row no path reaches
+// (kDeadLogOcc), decided before anything else of the row is asked for. Src hands over the row's inputs one by one:
+// RowInMemory loads each where it is first needed (nothing of a dead row but alpha / beta is read -- under a
+// restricting alignment lp is written only inside the alignment window), RowLoaded holds values loaded ahead.
+struct ArcWeights {
+    double wb, we;
+};
+
+template <class Src>
+__device__ __forceinline__ ArcWeights expect_weights(const Src &r, bool label_arc, double ll, double R, float ge,
+                                                     float gc) {
+    ArcWeights w{0.0, 0.0};
+    const double base = r.a_prev() - ll;
+    if (!row_live(base + r.beta0())) return w;
+    const double b1 = r.beta_blank();
+    const double b2 = r.beta_label();
+    const Lp l = r.lp();
+    // the two arc posteriors as row_coef forms them (fp64 cancellation, then v_exp_f32: relative error ~1e-6)
+    const float pb = fast_exp2((float)((l.b + base + b1) * kLog2eD));
+    const float pe = label_arc ? fast_exp2((float)((l.e + base + b2) * kLog2eD)) : 0.0f;
+    const double ap = r.A_prev();
+    if (pb != 0.0f) {  // (deviation of the paths through the arc from the mean: the fp64 cancellation first)
+        const double dev = ap + r.cost_blank() + r.Bk_blank() - R;
+        w.wb = (double)pb * ((double)gc - (double)ge * dev);
+    }
+    if (pe != 0.0f) {
+        const double dev = ap + r.cost_label() + r.Bk_label() - R;
+        w.we = (double)pe * ((double)gc - (double)ge * dev);
+    }
+    return w;
+}
+
+struct RowInMemory {
+    const DevProblem &p;
+    int t, S, s, W;
+    int64_t row, arow;  // the lattice row; the column's first row in the cost arrays (acts' row layout)
+    bool last;          // t == T - 1
+    __device__ __forceinline__ double a_prev() const { return alpha_prev(p, t, s, row, W); }
+    __device__ __forceinline__ double beta0() const { return p.beta[row]; }
+    __device__ __forceinline__ double beta_blank() const {
+        return last ? (s == S ? 0.0 : NEG_INF_D) : p.beta[row + W];
+    }
+    __device__ __forceinline__ double beta_label() const {
+        return (s == S) ? NEG_INF_D : (last ? (s + 1 == S ? 0.0 : NEG_INF_D) : p.beta[row + W + 1]);
+    }
+    __device__ __forceinline__ Lp lp() const { return p.lp[row]; }
+    __device__ __forceinline__ double A_prev() const { return (t == 0) ? 0.0 : p.ex_A[row - W]; }
+    __device__ __forceinline__ double cost_blank() const { return p.ex_wb ? (double)p.ex_wb[arow + s] : 0.0; }
+    __device__ __forceinline__ double cost_label() const { return p.ex_we ? (double)p.ex_we[arow + s] : 0.0; }
+    __device__ __forceinline__ double Bk_blank() const { return last ? 0.0 : p.ex_Bk[row + W]; }
+    __device__ __forceinline__ double Bk_label() const { return last ? 0.0 : p.ex_Bk[row + W + 1]; }
+};
+
+struct RowLoaded {
+    double am, b0, b1, b2, ap, k1, k2;
+    Lp l;
+    float cwb, cwe;
+    __device__ __forceinline__ double a_prev() const { return am; }
+    __device__ __forceinline__ double beta0() const { return b0; }
+    __device__ __forceinline__ double beta_blank() const { return b1; }
+    __device__ __forceinline__ double beta_label() const { return b2; }
+    __device__ __forceinline__ Lp lp() const { return l; }
+    __device__ __forceinline__ double A_prev() const { return ap; }
+    __device__ __forceinline__ double cost_blank() const { return (double)cwb; }
+    __device__ __forceinline__ double cost_label() const { return (double)cwe; }
+    __device__ __forceinline__ double Bk_blank() const { return k1; }
+    __device__ __forceinline__ double Bk_label() const { return k2; }
+};
+
+// The fused joint's coefficient launch (mrnnt_joint_expect_rows): Wb / We of every row of the monotonic band into
+// out_b / out_e (fp64 [N], the lattice's packed rows), for the expect-live row list (launch_row_list mode 3) and the
+// MFMA gradient pass (PathCoef reads them as p.alpha / p.beta). One wave per lattice column, lanes along s, grid-stride
+// over columns. A row whose two weights round to fp32 zeros -- what the gradient pass would stage -- holds exact 0.0
+// (dead, unreachable, outside a restricting alignment's window, underflow): it is not listed. Every in-band row of an
+// utterance whose ll is not finite holds NaN. Rows outside the band are not written.
+// The loads of a row do not depend on one another and none sits behind a branch: a lane past the band's end, the
+// first / last frame and s = S load a clamped address (the row itself, or the band's last row) and the boundary value
+// is selected afterwards, so the ten loads are issued together and waited for once (build_row's rule, mrnnt_joint.hip).
+// Everything they touch is allocated and initialised: alpha / beta / A / Bk over the band, lp zero-filled by the joint
+// forward, the cost arrays over the caller's grid (the label cost of s = S_b is addressed at s = S_b - 1; a value the
+// contract calls never-read -- S_b = 0, a dead row -- may be loaded and is then dropped by a select, never multiplied).
+template <bool WB, bool WE>
+__global__ __launch_bounds__(256) void expect_coef_kernel(DevProblem p, double *__restrict__ out_b,
+                                                          double *__restrict__ out_e) {
+    if (p.dyn && __builtin_amdgcn_readfirstlane(p.dyn->status)) return;  // failed lengths: nothing is touched
+    const int lane = threadIdx.x & 63;
+    for (int64_t col = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); col < p.num_cols; col += (int64_t)gridDim.x * 4) {
+        const int b = p.col_b[col];
+        const int T = p.T[b], S = p.S[b], W = S + 1;
+        const int t = (int)(col - p.col_off[b]);
+        const int64_t rowc = p.row_off[b] + (int64_t)t * W;
+        const int lo = max(0, t - (T - S)), hi = min(t, S);
+        const double ll = p.ll[b], R = p.ex_R[b];
+        const float ge = p.ex_ge ? p.ex_ge[b] : 0.0f, gc = p.ex_gc ? p.ex_gc[b] : 0.0f;
+        const bool fin = __builtin_isfinite(ll), first = t == 0, last = t == T - 1;
+        const int64_t arow = acts_col_base(p, b, t, rowc);
+        const int64_t up = first ? 0 : -(int64_t)W, dn = last ? 0 : (int64_t)W;  // the neighbour frames, clamped
+        for (int s0 = lo; s0 <= hi; s0 += 64) {
+            const bool in = s0 + lane <= hi;
+            const int s = min(s0 + lane, hi);  // lanes past the band work on its last row and store nothing
+            const int sn = min(s + 1, S);
+            const int64_t row = rowc + s;
+            RowLoaded r;
+            r.am = p.alpha[row + up];
+            r.b0 = p.beta[row];
+            r.b1 = p.beta[row + dn];
+            r.b2 = p.beta[rowc + dn + sn];
+            r.l = p.lp[row];
+            r.ap = p.ex_A[row + up];
+            r.k1 = p.ex_Bk[row + dn];
+            r.k2 = p.ex_Bk[rowc + dn + sn];
+            r.cwb = WB ? p.ex_wb[arow + s] : 0.0f;
+            r.cwe = WE ? p.ex_we[arow + max(min(s, S - 1), 0)] : 0.0f;
+            if (first) {
+                r.am = s == 0 ? 0.0 : NEG_INF_D;
+                r.ap = 0.0;
+            }
+            if (last) {
+                r.b1 = s == S ? 0.0 : NEG_INF_D;
+                r.b2 = s + 1 == S ? 0.0 : NEG_INF_D;
+                r.k1 = r.k2 = 0.0;
+            }
+            if (s == S) r.b2 = NEG_INF_D;
+            ArcWeights w = expect_weights(r, s < S, ll, R, ge, gc);
+            if ((float)w.wb == 0.0f && (float)w.we == 0.0f) w.wb = w.we = 0.0;
+            if (!fin) w.wb = w.we = __builtin_nan("");
+            if (in) {
+                out_b[row] = w.wb;
+                out_e[row] = w.we;
+            }
+        }
+    }
+}
+
 // The expected cost's rows for the shared streamers (mrnnt_grad.h): band = the loss's band; a row's two weights from
 // alpha / beta / A / Bk / lp / ll / R, the two costs and the two upstream scalars; the other rows exact zeros -- NaN
 // for an utterance whose ll is not finite. Slot, formula and scalar twin: WeightRows.
@@ -246,33 +387,14 @@ struct ExpectRows : WeightRows {
                                                  const int *lab_b) {
         Slot c{0.0f, 0.0f, 0.0f, 0.0f, kDeadRow};
         if (!col.fin || !(s >= col.lo && s <= col.hi)) return c;
-        const int W = S + 1;
         const int64_t row = rowc + s;
-        const double base = alpha_prev(p, t, s, row, W) - col.ll;
-        if (!row_live(base + p.beta[row])) return c;
-        const bool last = t == col.T - 1;
-        const double b1 = last ? (s == S ? 0.0 : NEG_INF_D) : p.beta[row + W];
-        const double b2 = (s == S) ? NEG_INF_D : (last ? (s + 1 == S ? 0.0 : NEG_INF_D) : p.beta[row + W + 1]);
-        const Lp l = p.lp[row];
-        // the two arc posteriors as row_coef forms them (fp64 cancellation, then v_exp_f32: relative error ~1e-6)
-        const float pb = fast_exp2((float)((l.b + base + b1) * kLog2eD));
-        const float pe = (s < S) ? fast_exp2((float)((l.e + base + b2) * kLog2eD)) : 0.0f;
-        const double ap = (t == 0) ? 0.0 : p.ex_A[row - W];
-        double wb = 0.0, we = 0.0;
-        if (pb != 0.0f) {  // (deviation of the paths through the arc from the mean: the fp64 cancellation first)
-            const double dev = ap + (p.ex_wb ? (double)p.ex_wb[col.arow + s] : 0.0) + (last ? 0.0 : p.ex_Bk[row + W]) - col.R;
-            wb = (double)pb * ((double)col.gc - (double)col.ge * dev);
-        }
-        if (pe != 0.0f) {
-            const double dev =
-                ap + (p.ex_we ? (double)p.ex_we[col.arow + s] : 0.0) + (last ? 0.0 : p.ex_Bk[row + W + 1]) - col.R;
-            we = (double)pe * ((double)col.gc - (double)col.ge * dev);
-        }
-        c.cb = (float)wb;
-        c.ce = (float)we;
+        const RowInMemory r{p, t, S, s, S + 1, row, col.arow, t == col.T - 1};
+        const ArcWeights w = expect_weights(r, s < S, col.ll, col.R, col.ge, col.gc);
+        c.cb = (float)w.wb;
+        c.ce = (float)w.we;
         if (c.cb == 0.0f && c.ce == 0.0f) return c;  // (lab is still kDeadRow: exact zeros, acts not read)
         c.c2 = p.den[row] * kLog2e;
-        c.wocc = (float)(wb + we);
+        c.wocc = (float)(w.wb + w.we);
         c.lab = slot_label(p, S, s, lab_b);
         return c;
     }
@@ -294,6 +416,19 @@ struct ExpectRows : WeightRows {
 
 hipError_t launch_expect(const DevProblem &p, int S_max, int with_bk, float *expected, hipStream_t stream) {
     if (!launch_by_width<true>(S_max + 1, ExpectLaunch{p, with_bk, expected, stream})) return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_expect_coef(const DevProblem &p, double *wb_out, double *we_out, hipStream_t stream) {
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((p.num_cols + 3) / 4, 1 << 20));
+    if (p.ex_wb && p.ex_we)
+        expect_coef_kernel<true, true><<<blocks, 256, 0, stream>>>(p, wb_out, we_out);
+    else if (p.ex_wb)
+        expect_coef_kernel<true, false><<<blocks, 256, 0, stream>>>(p, wb_out, we_out);
+    else if (p.ex_we)
+        expect_coef_kernel<false, true><<<blocks, 256, 0, stream>>>(p, wb_out, we_out);
+    else
+        expect_coef_kernel<false, false><<<blocks, 256, 0, stream>>>(p, wb_out, we_out);
     return hipGetLastError();
 }
 

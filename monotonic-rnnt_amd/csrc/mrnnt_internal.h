@@ -121,7 +121,9 @@ struct JointArgs {
 
 // Row lists over the lattice: mode 0 = every in-band row, mode 1 = live rows (needs alpha/beta/ll), mode 2 =
 // path-live rows (mrnnt_joint_path_*: the rows of the column's hull, p.min_s / p.max_s, whose path weights Wb / We in
-// p.alpha / p.beta are not both zero; nothing outside the hull is read).
+// p.alpha / p.beta are not both zero; nothing outside the hull is read), mode 3 = expect-live rows
+// (mrnnt_joint_expect_rows: the rows of the monotonic band whose weights Wb / We, which the caller's device problem
+// has in p.alpha / p.beta after launch_expect_coef, are not both zero -- NaN counts as non-zero; no hull).
 hipError_t launch_row_list(const DevProblem &p, int mode, int64_t *col_cnt, int *lcol, int *ls,
                            unsigned long long *total, hipStream_t stream);
 hipError_t launch_joint_forward(const DevProblem &p, const JointArgs &j, hipStream_t stream);
@@ -331,6 +333,10 @@ hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid
 // of g_e . expected + g_c . costs over the row policy ExpectRows.
 hipError_t launch_expect(const DevProblem &p, int S_max, int with_bk, float *expected, hipStream_t stream);
 hipError_t launch_expect_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
+// mrnnt_joint_expect_rows: the same two row weights Wb / We (fp64, ExpectRows' own function) of every row of the
+// monotonic band into wb_out / we_out [N] -- exact 0.0 where both round to fp32 zeros, NaN for a non-finite ll -- for
+// launch_row_list mode 3 and launch_joint_backward(path_coef) on a device problem whose alpha / beta point at them.
+hipError_t launch_expect_coef(const DevProblem &p, double *wb_out, double *we_out, hipStream_t stream);
 
 // The chase launch (mrnnt_chase.hip): log-softmax and alpha / beta recursion in one launch, the recursion consuming
 // columns as they are published. Ready flags: one 64-bit word per lattice column, holding the tag of the launch that

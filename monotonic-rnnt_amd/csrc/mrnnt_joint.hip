@@ -81,11 +81,13 @@ __device__ __forceinline__ f2 fast_tanh2(f2 x) {
 // ---------------------------------------------------------------------------------------------------------
 // row lists: entries (column, s) in column order, s ascending; mode 0 = in-band rows, 1 = live rows, 2 = path-live
 // rows (mrnnt_joint_path_rows): the rows of the column's hull whose path weights Wb / We (p.alpha / p.beta after
-// launch_path_coef) are not both zero
+// launch_path_coef) are not both zero, 3 = expect-live rows (mrnnt_joint_expect_rows): the rows of the monotonic band
+// whose weights Wb / We (launch_expect_coef; the launch's p.alpha / p.beta point at them) are not both zero -- there is
+// no hull, and a restricting alignment has already made the weights outside its window zero
 
 __device__ __forceinline__ bool list_pred(const DevProblem &p, int mode, int t, int s, int64_t row, int W,
                                           double ll) {
-    if (mode == 2) return p.alpha[row] != 0.0 || p.beta[row] != 0.0;
+    if (mode >= 2) return p.alpha[row] != 0.0 || p.beta[row] != 0.0;  // (NaN != 0: listed)
     if (mode == 0 || !p.occ_skip) return true;
     return row_live(alpha_prev(p, t, s, row, W) - ll + p.beta[row]);
 }
@@ -696,6 +698,8 @@ struct LossCoef {
 // (mrnnt_path.hip), with Wb / We in p.alpha / p.beta (launch_path_coef) and den from the forward. wocc = Wb + We is a
 // signed multiplier -- never a divisor: wocc = 0 with Wb = -We != 0 is a live row whose two corrections stay. Only
 // listed rows are staged (path-live: inside the hull), so nothing uninitialised is read.
+// Expected costs (mrnnt_joint_expect_backward) run the same class over the expect-live rows: their launch's p.alpha /
+// p.beta point at launch_expect_coef's two arrays.
 struct PathCoef {
     float c2, wocc, cb, ce;
     int lab;

@@ -3,7 +3,9 @@
 // mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors / mrnnt_joint_sample put the Viterbi launch / the
 // posterior read-out / the path sampler of the loss ABI behind the joint's log-softmax pass; mrnnt_joint_path_* score
 // given alignments (mrnnt_path.hip's walk / hull / score / coef launches around the joint pass over the hull rows) and
-// run the gradient pass over the path-live rows. Asynchronous on the caller's stream, no host synchronisation.
+// run the gradient pass over the path-live rows; mrnnt_joint_expect_* put the expectation recursion of
+// mrnnt_expect.hip behind the joint forward, form the expected cost's row weights (launch_expect_coef) and run the same
+// gradient pass over the expect-live rows. Asynchronous on the caller's stream, no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -208,13 +210,74 @@ PathArgs joint_path_args(const JointPathPlan &pp, void *ws, const int *alignment
     return path_args(ws, pp.off_valid, pp.off_carry, pp.off_min, pp.off_max, alignments_dev, num_paths, path_stride);
 }
 
-// mrnnt_joint_backward / mrnnt_joint_path_backward: the MFMA gradient pass over the rows of the last list built, with
-// the loss's row coefficients (alpha / beta / ll, times scale) or the path weights (path: Wb / We in alpha / beta).
-RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale, void *G,
-                          void *Hact, int64_t *bt_idx, int64_t *bs_idx, bool path, hipStream_t stream) {
+// mrnnt_joint_expect_*: the ordinary joint workspace of the same problem (a restricting alignment included), FOLLOWED
+// by the expectation state A / Bk (fp64 [N]) and R (fp64 [B]) and the two row-weight arrays Wb / We (fp64 [N]) of the
+// coefficient launch. mrnnt_joint_reduce / _reduce_pre / _dpre work on it unchanged, as on the path workspace.
+struct JointExpectPlan {
     JointPlan jl;
-    RNNTStatus st = make_joint_plan(jp, &jl);
+    size_t off_A = 0, off_Bk = 0, off_R = 0, off_wb = 0, off_we = 0, total = 0;
+};
+
+RNNTStatus make_joint_expect_plan(const mrnnt_joint_problem *jp, JointExpectPlan *ep) {
+    const RNNTStatus st = make_joint_plan(jp, &ep->jl);
     if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = ep->jl.base;
+    size_t o = ep->jl.total;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o = align_up(o + bytes);
+        return at;
+    };
+    ep->off_A = take(sizeof(double) * (size_t)pl.N);
+    ep->off_Bk = take(sizeof(double) * (size_t)pl.N);
+    ep->off_R = take(sizeof(double) * (size_t)pl.B);
+    ep->off_wb = take(sizeof(double) * (size_t)pl.N);
+    ep->off_we = take(sizeof(double) * (size_t)pl.N);
+    ep->total = o;
+    return RNNT_STATUS_SUCCESS;
+}
+
+// the cost arrays' grid [B, grid_T, grid_S1] holds every row (not looked at when neither array is given)
+RNNTStatus check_cost_grid(const Plan &pl, const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
+                           int64_t grid_S1) {
+    if ((blank_cost_dev || label_cost_dev) && (grid_T < pl.T_max || grid_S1 < (int64_t)pl.S_max + 1))
+        return fail(RNNT_STATUS_INVALID_VALUE, "cost grid [" + std::to_string(grid_T) + ", " + std::to_string(grid_S1) +
+                                                   "] smaller than [max T, max S + 1] = [" + std::to_string(pl.T_max) +
+                                                   ", " + std::to_string(pl.S_max + 1) + "]");
+    return RNNT_STATUS_SUCCESS;
+}
+
+// The device problem of the expectation launches: the packed lattice of the joint, the state arrays, and the cost
+// arrays on the caller's grid -- only acts_col_base, which the expectation kernels address the costs through, takes
+// the padded mapping (as mrnnt_joint_posteriors' outputs do).
+DevProblem joint_expect_dev(const mrnnt_problem *p, const JointExpectPlan &ep, void *ws, const float *blank_cost_dev,
+                            const float *label_cost_dev, int64_t grid_T, int64_t grid_S1) {
+    DevProblem d = make_dev(p, ep.jl.base, ws);
+    d.ex_A = carve<double>(ws, ep.off_A);
+    d.ex_Bk = carve<double>(ws, ep.off_Bk);
+    d.ex_R = carve<double>(ws, ep.off_R);
+    d.ex_wb = blank_cost_dev;
+    d.ex_we = label_cost_dev;
+    if (blank_cost_dev || label_cost_dev) {
+        d.pad_T = grid_T;
+        d.pad_S1 = grid_S1;
+    }
+    return d;
+}
+
+// mrnnt_joint_backward / mrnnt_joint_path_backward / mrnnt_joint_expect_backward: the MFMA gradient pass over the rows
+// of the last list built, with the loss's row coefficients (alpha / beta / ll, times scale), the path weights (path:
+// Wb / We in alpha / beta) or the expected cost's (expect: the path coefficients on a device problem whose alpha / beta
+// point at the coefficient launch's Wb / We arrays -- the same kernel instantiation).
+enum JointCoef { kCoefLoss, kCoefPath, kCoefExpect };
+
+RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale, void *G,
+                          void *Hact, int64_t *bt_idx, int64_t *bs_idx, JointCoef coef, hipStream_t stream) {
+    const bool path = coef == kCoefPath;
+    JointExpectPlan ep;
+    RNNTStatus st = make_joint_expect_plan(jp, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const JointPlan &jl = ep.jl;
     if (path && jp->alignment)
         return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL)");
     if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
@@ -226,6 +289,10 @@ RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_liv
         return fail(RNNT_STATUS_INVALID_VALUE, "G / Hact must be 16-byte aligned");
     const mrnnt_problem p = base_problem(jp);
     DevProblem d = make_dev(&p, jl.base, ws);
+    if (coef == kCoefExpect) {
+        d.alpha = carve<double>(ws, ep.off_wb);
+        d.beta = carve<double>(ws, ep.off_we);
+    }
     JointArgs j = joint_args(jp, jl, ws, n_live);
     j.n_dev = jp->live_count_dev;  // n_live a host bound: workgroups past the device count exit (their rows zeroed below)
     j.G = static_cast<unsigned short *>(G);
@@ -242,7 +309,7 @@ RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_liv
         return fail(RNNT_STATUS_INVALID_VALUE, "dbias needs a bias (the workspace holds its partial sums only then)");
     if (jp->dbias) j.dbias_part = carve<float>(ws, jl.off_dbias);
     hipError_t e = timed(K_JOINT_BWD, stream, [&] {
-        const hipError_t eb = launch_joint_backward(d, j, stream, path);
+        const hipError_t eb = launch_joint_backward(d, j, stream, coef != kCoefLoss);
         if (eb != hipSuccess || !jp->live_count_dev) return eb;
         return launch_joint_tail_zero(j.G, jp->V, j.Hact, j.hact_ld, n_live, jp->live_count_dev, stream);
     });
@@ -366,7 +433,7 @@ RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *jp, void *ws, unsign
 
 RNNTStatus mrnnt_joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale,
                                 void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
-    return joint_backward(jp, ws, n_live, grad_scale, G, Hact, bt_idx, bs_idx, false, stream);
+    return joint_backward(jp, ws, n_live, grad_scale, G, Hact, bt_idx, bs_idx, kCoefLoss, stream);
 }
 
 RNNTStatus mrnnt_joint_path_workspace_size(const mrnnt_joint_problem *jp, int num_paths, size_t *bytes) {
@@ -453,7 +520,71 @@ RNNTStatus mrnnt_joint_path_rows(const mrnnt_joint_problem *jp, void *ws, size_t
 
 RNNTStatus mrnnt_joint_path_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_rows, void *G, void *Hact,
                                      int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
-    return joint_backward(jp, ws, n_rows, nullptr, G, Hact, bt_idx, bs_idx, true, stream);
+    return joint_backward(jp, ws, n_rows, nullptr, G, Hact, bt_idx, bs_idx, kCoefPath, stream);
+}
+
+RNNTStatus mrnnt_joint_expect_workspace_size(const mrnnt_joint_problem *jp, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    JointExpectPlan ep;
+    const RNNTStatus st = make_joint_expect_plan(jp, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = ep.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_expect_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes,
+                                      const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
+                                      int64_t grid_S1, float *expected_dev, float *costs_dev, int with_grad,
+                                      hipStream_t stream) {
+    JointExpectPlan ep;
+    RNNTStatus st = make_joint_expect_plan(jp, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = ep.jl.base;
+    if ((st = check_cost_grid(pl, blank_cost_dev, label_cost_dev, grid_T, grid_S1)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    // the joint's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
+    if ((st = mrnnt_joint_forward(jp, ws, ws_bytes, costs_dev, with_grad ? 1 : 0, stream)) != RNNT_STATUS_SUCCESS)
+        return st;
+    const mrnnt_problem p = base_problem(jp);
+    const DevProblem d = joint_expect_dev(&p, ep, ws, blank_cost_dev, label_cost_dev, grid_T, grid_S1);
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_expect(d, pl.S_max, with_grad ? 1 : 0, expected_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "expectation recursion kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_expect_rows(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes,
+                                   const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
+                                   int64_t grid_S1, const float *grad_expected_dev, const float *grad_costs_dev,
+                                   unsigned long long *count_dev, hipStream_t stream) {
+    JointExpectPlan ep;
+    RNNTStatus st = make_joint_expect_plan(jp, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const JointPlan &jl = ep.jl;
+    if ((st = check_cost_grid(jl.base, blank_cost_dev, label_cost_dev, grid_T, grid_S1)) != RNNT_STATUS_SUCCESS)
+        return st;
+    if (!count_dev) return fail(RNNT_STATUS_INVALID_VALUE, "count is null");
+    if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    const mrnnt_problem p = base_problem(jp);
+    DevProblem d = joint_expect_dev(&p, ep, ws, blank_cost_dev, label_cost_dev, grid_T, grid_S1);
+    d.ex_ge = grad_expected_dev;
+    d.ex_gc = grad_costs_dev;
+    double *wb = carve<double>(ws, ep.off_wb), *we = carve<double>(ws, ep.off_we);
+    hipError_t e = timed(K_DP, stream, [&] { return launch_expect_coef(d, wb, we, stream); });
+    if (e != hipSuccess) return fail_hip(e, "expected-cost coefficient kernel");
+    d.alpha = wb;  // the list's (and the gradient pass's) view: the two weights where the path scores keep theirs
+    d.beta = we;
+    e = launch_row_list(d, 3, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
+                        count_dev, stream);
+    if (e != hipSuccess) return fail_hip(e, "expect-live row list kernels");
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_joint_expect_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_rows, void *G, void *Hact,
+                                       int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
+    return joint_backward(jp, ws, n_rows, nullptr, G, Hact, bt_idx, bs_idx, kCoefExpect, stream);
 }
 
 // pre: dH already holds dpre (Hact unused; the kRedPre kernel form)

@@ -1,6 +1,7 @@
 """PyTorch surface of the MI355X monotonic RNN-T loss (drop-in for the reference's pytorch_binding)."""
-from .monotonic_rnnt_joint import (MonotonicRNNTJointFunction, MonotonicRNNTJointPathFunction,
-                                   monotonic_rnnt_joint_align, monotonic_rnnt_joint_loss,
+from .monotonic_rnnt_joint import (MonotonicRNNTJointExpectedCostFunction, MonotonicRNNTJointFunction,
+                                   MonotonicRNNTJointPathFunction, monotonic_rnnt_joint_align,
+                                   monotonic_rnnt_joint_expected_cost, monotonic_rnnt_joint_loss,
                                    monotonic_rnnt_joint_path_loss, monotonic_rnnt_joint_posteriors,
                                    monotonic_rnnt_joint_sample)
 from .monotonic_rnnt_op import (MonotonicRNNTExpectedCostFunction, MonotonicRNNTFunction, MonotonicRNNTLoss,
@@ -13,4 +14,5 @@ __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", 
            "monotonic_rnnt_posteriors", "monotonic_rnnt_joint_align", "monotonic_rnnt_joint_posteriors",
            "monotonic_rnnt_sample", "monotonic_rnnt_joint_sample", "MonotonicRNNTPathFunction",
            "monotonic_rnnt_path_loss", "MonotonicRNNTJointPathFunction", "monotonic_rnnt_joint_path_loss",
-           "MonotonicRNNTExpectedCostFunction", "monotonic_rnnt_expected_cost"]
+           "MonotonicRNNTExpectedCostFunction", "monotonic_rnnt_expected_cost",
+           "MonotonicRNNTJointExpectedCostFunction", "monotonic_rnnt_joint_expected_cost"]

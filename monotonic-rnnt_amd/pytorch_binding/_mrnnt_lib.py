@@ -187,6 +187,10 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_joint_path_forward": (i, [JP, vp, sz, vp, i, i64, vp, vp]),
         "mrnnt_joint_path_rows": (i, [JP, vp, sz, vp, i, i64, vp, vp, vp]),
         "mrnnt_joint_path_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp]),
+        "mrnnt_joint_expect_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
+        "mrnnt_joint_expect_forward": (i, [JP, vp, sz, vp, vp, i64, i64, vp, vp, i, vp]),
+        "mrnnt_joint_expect_rows": (i, [JP, vp, sz, vp, vp, i64, i64, vp, vp, vp, vp]),
+        "mrnnt_joint_expect_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp]),
         "mrnnt_last_error": (ctypes.c_char_p, []),
         "mrnnt_version": (i, []),
         "mrnnt_fill_zero": (i, [vp, sz, vp]),

@@ -256,6 +256,77 @@ class _JointPrepared:
                                                    None, self.stream()), "mrnnt_joint_path_backward")
         return G[:n], Hact[:n]
 
+    def cost_grid(self, blank_costs, label_costs):
+        """The two per-arc cost arrays as mrnnt_joint_expect_* take them: (wb, we, grid_T, grid_S1), fp32 [B, grid_T,
+        grid_S1] on the device or None."""
+        out, shape = [], None
+        need = (self.B, int(self.T_host.max(initial=1)), int(self.S_host.max(initial=0)) + 1)
+        for what, x in (("blank_costs", blank_costs), ("label_costs", label_costs)):
+            if x is None:
+                out.append(None)
+                continue
+            if x.dim() != 3 or x.size(0) != self.B or x.size(1) < need[1] or x.size(2) < need[2]:
+                raise RuntimeError(f"monotonic_rnnt_joint_expected_cost: {what} must be [B, grid_T, grid_S1] with "
+                                   f"B = {need[0]}, grid_T >= {need[1]}, grid_S1 >= {need[2]}, got {tuple(x.shape)}")
+            if shape is not None and tuple(x.shape) != shape:
+                raise RuntimeError("monotonic_rnnt_joint_expected_cost: blank_costs and label_costs must have the "
+                                   f"same shape, got {shape} and {tuple(x.shape)}")
+            shape = tuple(x.shape)
+            out.append(x.detach().to(self.device, torch.float32).contiguous())
+        gT, gS1 = (shape[1], shape[2]) if shape is not None else (0, 0)
+        return out[0], out[1], gT, gS1
+
+    def expect_forward(self, wb, we, gT, gS1, with_grad: bool):
+        """(expected [B], costs [B], workspace): mrnnt_joint_expect_forward on a workspace of
+        mrnnt_joint_expect_workspace_size bytes."""
+        lib = _L.load()
+        n = ctypes.c_size_t(0)
+        _L.check(lib.mrnnt_joint_expect_workspace_size(ctypes.byref(self.problem), ctypes.byref(n)),
+                 "joint_expect_workspace_size")
+        with torch.cuda.device(self.device):
+            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            expected = torch.empty(self.B, dtype=torch.float32, device=self.device)
+            costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
+            _L.check(lib.mrnnt_joint_expect_forward(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(wb), _vp(we),
+                                                    gT, gS1, _vp(expected), _vp(costs), 1 if with_grad else 0,
+                                                    self.stream()), "mrnnt_joint_expect_forward")
+        return expected, costs, ws
+
+    def expect_rows(self, ws, wb, we, gT, gS1, ge, gc):
+        """After expect_forward(with_grad=True): the row weights of sum_b ge expected + gc costs and the list of the
+        expect-live rows; returns their count (int64 [1], on the device)."""
+        with torch.cuda.device(self.device):
+            cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
+            _L.check(_L.load().mrnnt_joint_expect_rows(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(wb),
+                                                       _vp(we), gT, gS1, _vp(ge), _vp(gc), _vp(cnt), self.stream()),
+                     "mrnnt_joint_expect_rows")
+        return cnt
+
+    def expect_backward_rows(self, ws, wb, we, gT, gS1, ge, gc, bias_column=False, dbias=None, capturable=False):
+        """backward_rows for the expected cost: (G [n, V], Hact [n, H or _HACT_LD[H]]) over the expect-live rows. By
+        default one 8-byte read-back of their count sizes the buffers; capturable: they are sized by the in-band rows
+        (mrnnt_joint_row_bound), the kernels take the count from the device and the rows past it are zeros."""
+        lib = _L.load()
+        cnt = self.expect_rows(ws, wb, we, gT, gS1, ge, gc)
+        with torch.cuda.device(self.device):
+            if capturable:
+                nb = ctypes.c_int64(0)
+                _L.check(lib.mrnnt_joint_row_bound(ctypes.byref(self.problem), ctypes.byref(nb)), "joint_row_bound")
+                n = nb.value
+                self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
+                self.problem.live_count_dev = cnt.data_ptr()
+            else:
+                n = int(cnt.item())
+                self.problem.live_count_dev = None
+            G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
+            ld = _HACT_LD[self.H] if bias_column else self.H
+            self.problem.hact_ld = ld
+            Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
+            self.problem.dbias = _vp(dbias)
+            _L.check(lib.mrnnt_joint_expect_backward(ctypes.byref(self.problem), _vp(ws), n, _vp(G), _vp(Hact), None,
+                                                     None, self.stream()), "mrnnt_joint_expect_backward")
+        return G[:n], Hact[:n]
+
     def dpre(self, G, Hact):
         """dpre = (G weight) * (1 - Hact^2), bf16 [n, H], on the library's hand-written MFMA tiles (mrnnt_joint_dpre)."""
         n = G.shape[0]
@@ -479,13 +550,18 @@ class MonotonicRNNTJointPathFunction(torch.autograd.Function):
         bias_col, fused_b, db = _dbias_plan(ctx, prep)
         G, Hact = prep.path_backward_rows(ws, al, w, bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
         if G.shape[0] == 0:  # no path-live row (all-zero weights, no valid path): every gradient is exactly zero
-            need = ctx.needs_input_grad
-            zero = lambda x, dt: torch.zeros(x.shape, dtype=dt, device=prep.device)  # noqa: E731
-            d_b = zero(prep.bias, ctx.bias_dtype) if ctx.bias_dtype is not None and need[3] else None
-            return (zero(prep.enc, prep.enc.dtype) if need[0] else None,
-                    zero(prep.pred, prep.pred.dtype) if need[1] else None,
-                    zero(prep.weight, prep.weight.dtype) if need[2] else None, d_b) + (None,) * 6
+            return _zero_grads(ctx, prep) + (None,) * 6
         return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 6
+
+
+def _zero_grads(ctx, prep):
+    """(d_enc, d_pred, d_weight, d_bias) of a backward whose row list is empty: exact zeros, nothing launched."""
+    need = ctx.needs_input_grad
+    zero = lambda x, dt: torch.zeros(x.shape, dtype=dt, device=prep.device)  # noqa: E731
+    d_b = zero(prep.bias, ctx.bias_dtype) if ctx.bias_dtype is not None and need[3] else None
+    return (zero(prep.enc, prep.enc.dtype) if need[0] else None,
+            zero(prep.pred, prep.pred.dtype) if need[1] else None,
+            zero(prep.weight, prep.weight.dtype) if need[2] else None, d_b)
 
 
 def monotonic_rnnt_joint_path_loss(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
@@ -518,6 +594,75 @@ def monotonic_rnnt_joint_path_loss(enc: torch.Tensor, pred: torch.Tensor, weight
     out = MonotonicRNNTJointPathFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
                                                label_lengths, al, blank_label, capturable)
     return out.squeeze(1) if alignments.dim() == 2 else out
+
+
+class MonotonicRNNTJointExpectedCostFunction(torch.autograd.Function):
+    """Expected path costs and the loss under the fused joint, with gradients for enc, pred, weight and bias
+    (mrnnt_joint_expect_forward / _rows / _backward, include/mrnnt.h): apply(enc, pred, weight, bias, labels,
+    input_lengths, label_lengths, blank_costs, label_costs, blank_label=0, alignment=None,
+    max_distance_from_alignment=0, capturable=None) -> (expected [B], costs [B]). The two upstream gradients go into one
+    set of row coefficients: one row list, one gradient pass, one chain."""
+
+    @staticmethod
+    def forward(ctx, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_costs=None, label_costs=None,
+                blank_label=0, alignment=None, max_distance_from_alignment=0, capturable=None):
+        prep = _JointPrepared(enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment,
+                              max_distance_from_alignment)
+        wb, we, gT, gS1 = prep.cost_grid(blank_costs, label_costs)
+        need = any(ctx.needs_input_grad[:4])
+        expected, costs, ws = prep.expect_forward(wb, we, gT, gS1, with_grad=need)
+        if need:
+            # the workspace holds the loss's state, den of the rows the forward computed, and A / Bk / R
+            ctx.save_for_backward(enc, pred, weight, ws)
+            ctx.prep, ctx.costs_grid = prep, (wb, we, gT, gS1)
+            ctx.bias_dtype = None if bias is None else bias.dtype
+            ctx.capturable = capturable
+        return expected, costs
+
+    @staticmethod
+    def backward(ctx, grad_expected, grad_costs):
+        prep, ws = ctx.prep, ctx.saved_tensors[3]
+        up = lambda g: None if g is None else g.detach().to(prep.device, torch.float32).contiguous()  # noqa: E731
+        bias_col, fused_b, db = _dbias_plan(ctx, prep)
+        G, Hact = prep.expect_backward_rows(ws, *ctx.costs_grid, up(grad_expected), up(grad_costs),
+                                            bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
+        if G.shape[0] == 0:  # no expect-live row (both upstreams zero, only single-path utterances under g_c = 0)
+            return _zero_grads(ctx, prep) + (None,) * 9
+        return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 9
+
+
+def monotonic_rnnt_joint_expected_cost(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                                       bias: Optional[torch.Tensor], labels: torch.Tensor,
+                                       input_lengths: torch.Tensor, label_lengths: torch.Tensor,
+                                       blank_costs: Optional[torch.Tensor] = None,
+                                       label_costs: Optional[torch.Tensor] = None, blank_label: int = 0,
+                                       alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
+                                       capturable: Optional[bool] = None):
+    """The exact expectation of an arc-additive path cost under the joint network tanh(enc + pred) @ weight.T + bias,
+    and the loss of the same inputs, without materialising the logits: monotonic_rnnt_expected_cost of the acts
+    monotonic_rnnt_joint_loss never stores, both outputs differentiable in enc, pred, weight and bias (each in its own
+    dtype) -- a latency regulariser or a minimum-risk term for a model trained through the fused joint:
+
+        t = torch.arange(enc.size(1), device=enc.device).view(1, -1, 1).expand(B, enc.size(1), pred.size(1))
+        latency, costs = monotonic_rnnt_joint_expected_cost(enc, pred, weight, bias, labels, T, S, label_costs=t.float())
+        (costs + 0.01 * latency).sum().backward()      # one row list, one gradient pass, one dweight / dH GEMM, one reduce
+
+    enc / pred / weight / bias / labels / lengths / alignment / max_distance_from_alignment / capturable as
+    monotonic_rnnt_joint_loss takes them (the bf16 cast, H in JOINT_H, GPU only); with `alignment` the expectation is
+    under the restricted distribution. blank_costs / label_costs: float [B, grid_T, grid_S1], grid_T >= max T_b,
+    grid_S1 >= max S_b + 1 -- the grid monotonic_rnnt_joint_posteriors returns blank / label on: the cost of the blank /
+    label arc out of row (b, t, s); either may be None (all zeros), both given have the same shape; signed costs are
+    fine; label_costs at s = S_b and anything at t >= T_b or s > S_b is ignored. The costs are not differentiated (their
+    gradient is monotonic_rnnt_joint_posteriors' blank / label).
+
+    Returns (expected, costs), float32 [B]; costs is monotonic_rnnt_joint_loss's, bit for bit. The backward of any
+    function of the two is one chain over the rows whose coefficients are not both zero. An utterance without a finite
+    cost has a NaN expected value and NaN gradients; the others' expected and costs are unaffected. Results are bitwise
+    reproducible."""
+    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
+    return MonotonicRNNTJointExpectedCostFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels,
+                                                        input_lengths, label_lengths, blank_costs, label_costs,
+                                                        blank_label, alignment, max_distance_from_alignment, capturable)
 
 
 def _bf16(x):
@@ -593,4 +738,5 @@ def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: t
 
 __all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_joint_align",
            "monotonic_rnnt_joint_posteriors", "monotonic_rnnt_joint_sample", "MonotonicRNNTJointPathFunction",
-           "monotonic_rnnt_joint_path_loss"]
+           "monotonic_rnnt_joint_path_loss", "MonotonicRNNTJointExpectedCostFunction",
+           "monotonic_rnnt_joint_expected_cost"]
