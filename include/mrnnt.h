@@ -317,6 +317,42 @@ RNNTStatus mrnnt_expect_backward_tracked(const mrnnt_problem *p, void *workspace
                                          const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
                                          unsigned char *row_state, int64_t row_state_len, hipStream_t stream);
 
+/* ---- factorised blank (the hybrid autoregressive transducer's output distribution; an addition to version 13:
+ * MRNNT_VERSION and the structs are unchanged, callers probe for the symbols) ------------------------------------
+ * The same lattice, band, alignment restriction, recursion and cost as mrnnt_forward, over another distribution per
+ * row z: blank (index b = p->blank, anywhere in [0, V)) is a Bernoulli on its own logit and the labels are a softmax
+ * over the other V - 1 logits,
+ *     lp_blank = log sigmoid(z_b),    lp_label = log sigmoid(-z_b) + z_l - LSE_{v != b} z_v.
+ * With cb / ce the blank-arc / label-arc posteriors of a row (mrnnt_posteriors' blank_post / label_post), the gradient
+ * mrnnt_hat_backward writes, times grad_scale, is
+ *     g[b] = ce sigmoid(z_b) - cb sigmoid(-z_b),    g[v != b] = ce (softmax_{u != b}(z)[v] - [v == label(s)])
+ * (at s = S_b: ce = 0, only g[b] is non-zero). A row whose ce and blank element are both zero in fp32 is stored as
+ * exact zeros without reading its acts. LSE_{v != b} keeps z_b out of the max and the sum (nothing is subtracted from a
+ * whole-row sum), each sigmoid is formed by itself in its stable form: a blank logit of +-100 over N(0,1) labels loses
+ * nothing. The passes move exactly the bytes of mrnnt_forward / mrnnt_backward.
+ * Non-finite logits keep the loss's meaning: a -inf label logit or z_b = -inf is "no such arc" (+inf cost when every
+ * path needs it); a NaN or +inf logit in an utterance's band, z_b = +inf included, makes that utterance's cost NaN;
+ * the other utterances are bit-identical either way. A label equal to blank is no label arc. A -inf on any other
+ * logit only removes that entry's mass; a row whose non-blank logits are all -inf (every row at V = 1) has no label
+ * arc (-inf, not NaN) and an unchanged blank arc, and den' = +inf there.
+ * mrnnt_hat_forward / mrnnt_hat_backward / mrnnt_hat_backward_tracked / mrnnt_hat_align take the arguments, the host
+ * checks, the layouts, element types, device-resident lengths, alignment restriction, row state and profile slots of
+ * mrnnt_forward / mrnnt_backward / mrnnt_backward_tracked / mrnnt_align, and the workspace is mrnnt_workspace_size(p)
+ * bytes. The forward never takes the single-launch (chase) form. mrnnt_posteriors and mrnnt_sample read only lp /
+ * alpha / beta / ll and work unchanged on the workspace of mrnnt_hat_forward(with_beta = 1); mrnnt_backward on such a
+ * workspace (or mrnnt_hat_backward after mrnnt_forward) is an error the library cannot detect. mrnnt_read_state's and
+ * mrnnt_read_denoms' den is -LSE_{v != b} on the rows a factorised forward reduced. The fused joint, mrnnt_path_* and
+ * mrnnt_expect_* have no factorised form yet. */
+RNNTStatus mrnnt_hat_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, float *costs_dev,
+                             int with_beta, hipStream_t stream);
+RNNTStatus mrnnt_hat_backward(const mrnnt_problem *p, const void *workspace, const float *grad_scale, void *grads,
+                              hipStream_t stream);
+RNNTStatus mrnnt_hat_backward_tracked(const mrnnt_problem *p, const void *workspace, const float *grad_scale,
+                                      void *grads, unsigned char *row_state, int64_t row_state_len,
+                                      hipStream_t stream);
+RNNTStatus mrnnt_hat_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out_dev,
+                           int64_t out_stride, float *costs_dev, hipStream_t stream);
+
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *workspace, double *ll_fwd_dev, double *ll_bwd_dev,
@@ -412,6 +448,17 @@ RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *workspace, siz
 RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
                                      const float *blank_cost, const float *label_cost, const float *grad_expected,
                                      const float *grad_costs, float *grads, int num_threads);
+
+/* mrnnt_hat_forward / mrnnt_hat_backward / mrnnt_hat_align for the host implementation: host buffers (fp32 acts),
+ * mrnnt_cpu_workspace_size bytes of workspace, the same formulas, masking, dead-row rule and non-finite rules in fp64
+ * with the library exp / log1p. mrnnt_cpu_posteriors and mrnnt_cpu_sample work unchanged after
+ * mrnnt_cpu_hat_forward(with_beta = 1). grads may be acts itself (in place), as in mrnnt_cpu_backward. */
+RNNTStatus mrnnt_cpu_hat_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, float *costs,
+                                 int with_beta, int num_threads);
+RNNTStatus mrnnt_cpu_hat_backward(const mrnnt_problem *p, const void *workspace, const float *grad_scale, float *grads,
+                                  int num_threads);
+RNNTStatus mrnnt_cpu_hat_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out,
+                               int64_t out_stride, float *costs, int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the

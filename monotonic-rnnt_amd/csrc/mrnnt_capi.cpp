@@ -53,29 +53,17 @@ bool copy_out(void *dst, const void *src, size_t bytes, hipStream_t stream) {
     return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
 }
 
-}  // namespace
-
-extern "C" {
-
-// mrnnt_version, mrnnt_last_error, mrnnt_lattice_bytes / mrnnt_lattice_host: mrnnt_entry.cpp (host-only)
-
-RNNTStatus mrnnt_workspace_size(const mrnnt_problem *p, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    Plan pl;
-    const RNNTStatus st = make_plan(p, &pl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pl.total;
-    return RNNT_STATUS_SUCCESS;
-}
-
-RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
-                         hipStream_t stream) {
+// mrnnt_forward / mrnnt_hat_forward. hat: the factorised-blank log-softmax (DevProblem::hat) on every route but the
+// chase launch, which has no factorised body: such a call takes the separate log-softmax + recursion.
+RNNTStatus forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
+                        hipStream_t stream, bool hat) {
     Plan pl;
     RNNTStatus st = make_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, pl.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
+    d.hat = hat ? 1 : 0;
     hipError_t e = hipSuccess;
     // device-resident lengths of a small batch without an alignment: planned inside the log-softmax launch itself
     // (every wave holds the lengths in registers, walk_columns in mrnnt_device.h) -- no separate setup kernel, whose
@@ -91,7 +79,7 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, floa
     }
     // no alignment: the forward as one launch, the recursion chasing the log-softmax (mrnnt_chase.hip), where it has a
     // body for these rows and pays (chase_pays); with device lengths the launch also plans and validates them
-    if (tuning().chase && chase_body(d, pl.elem) >= 0 && chase_pays(pl, with_beta) && (!pl.dyn || fused)) {
+    if (!hat && tuning().chase && chase_body(d, pl.elem) >= 0 && chase_pays(pl, with_beta) && (!pl.dyn || fused)) {
         ChaseArgs ca;
         ca.flags = carve<unsigned long long>(ws, pl.off_flags);
         // device lengths: the slots come from the lengths on the device; the grid from the plan's column bound
@@ -134,13 +122,9 @@ RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, floa
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
-                          hipStream_t stream) {
-    return mrnnt_backward_tracked(p, ws, grad_scale, grads, nullptr, 0, stream);
-}
-
-RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
-                                  unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+// mrnnt_backward_tracked / mrnnt_hat_backward_tracked. hat: the row policy HatRows (mrnnt_hat.hip).
+RNNTStatus backward_impl(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                         unsigned char *row_state, int64_t row_state_len, hipStream_t stream, bool hat) {
     Plan pl;
     RNNTStatus st = make_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -151,11 +135,14 @@ RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *ws, const 
     if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
     d.row_state = row_state;
     d.col_mul = column_order(pl, 2);
-    // grad_variant 3 sweeps rows (packed layout only), the others walk lattice columns
-    const int grid = (tuning().grad_variant == 3 && pl.pad_S1 == 0)
+    // grad_variant 3 sweeps rows (packed layout only), the others walk lattice columns (the factorised gradient always)
+    const int grid = (!hat && tuning().grad_variant == 3 && pl.pad_S1 == 0)
                          ? streaming_grid(pl.N, std::max(1, tuning().grad_grid_per_cu))
                          : streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    hipError_t e = timed(K_GRAD, stream, [&] { return launch_grad(d, pl.elem, grad_scale, grads, grid, stream); });
+    hipError_t e = timed(K_GRAD, stream, [&] {
+        return hat ? launch_hat_grad(d, pl.elem, grad_scale, grads, grid, stream)
+                   : launch_grad(d, pl.elem, grad_scale, grads, grid, stream);
+    });
     if (e != hipSuccess) return fail_hip(e, "gradient kernel");
     if (pl.pad_S1 != 0) {
         e = launch_pad_zero(d, pl.elem, grads, stream);
@@ -164,15 +151,9 @@ RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *ws, const 
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, void *grads,
-                               const float *grad_scale, hipStream_t stream) {
-    RNNTStatus st = mrnnt_forward(p, ws, ws_bytes, costs_dev, grads != nullptr, stream);
-    if (st != RNNT_STATUS_SUCCESS || grads == nullptr) return st;
-    return mrnnt_backward(p, ws, grad_scale, grads, stream);
-}
-
-RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out_dev, int64_t out_stride,
-                       float *costs_dev, hipStream_t stream) {
+// mrnnt_align / mrnnt_hat_align
+RNNTStatus align_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out_dev, int64_t out_stride,
+                      float *costs_dev, hipStream_t stream, bool hat) {
     Plan pl;
     RNNTStatus st = make_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -181,6 +162,7 @@ RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *a
     if ((st = check_row_stride("alignment_out", out_stride, "input", pl.T_max, pl.dyn, 1)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, pl.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
+    d.hat = hat ? 1 : 0;
     // the separate-kernel route of mrnnt_forward: setup, alignment band, log-softmax, then the Viterbi launch in the
     // recursion's place (no chase, no planning inside the log-softmax launch)
     LatticeOpts o;
@@ -193,6 +175,68 @@ RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *a
         timed(K_DP, stream, [&] { return launch_viterbi(d, pl.S_max, alignment_out_dev, out_stride, costs_dev, stream); });
     if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
     return RNNT_STATUS_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+// mrnnt_version, mrnnt_last_error, mrnnt_lattice_bytes / mrnnt_lattice_host: mrnnt_entry.cpp (host-only)
+
+RNNTStatus mrnnt_workspace_size(const mrnnt_problem *p, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    Plan pl;
+    const RNNTStatus st = make_plan(p, &pl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = pl.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
+                         hipStream_t stream) {
+    return forward_impl(p, ws, ws_bytes, costs_dev, with_beta, stream, false);
+}
+
+RNNTStatus mrnnt_hat_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
+                             hipStream_t stream) {
+    return forward_impl(p, ws, ws_bytes, costs_dev, with_beta, stream, true);
+}
+
+RNNTStatus mrnnt_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                          hipStream_t stream) {
+    return mrnnt_backward_tracked(p, ws, grad_scale, grads, nullptr, 0, stream);
+}
+
+RNNTStatus mrnnt_backward_tracked(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                                  unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+    return backward_impl(p, ws, grad_scale, grads, row_state, row_state_len, stream, false);
+}
+
+RNNTStatus mrnnt_hat_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                              hipStream_t stream) {
+    return backward_impl(p, ws, grad_scale, grads, nullptr, 0, stream, true);
+}
+
+RNNTStatus mrnnt_hat_backward_tracked(const mrnnt_problem *p, const void *ws, const float *grad_scale, void *grads,
+                                      unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+    return backward_impl(p, ws, grad_scale, grads, row_state, row_state_len, stream, true);
+}
+
+RNNTStatus mrnnt_cost_and_grad(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, void *grads,
+                               const float *grad_scale, hipStream_t stream) {
+    RNNTStatus st = mrnnt_forward(p, ws, ws_bytes, costs_dev, grads != nullptr, stream);
+    if (st != RNNT_STATUS_SUCCESS || grads == nullptr) return st;
+    return mrnnt_backward(p, ws, grad_scale, grads, stream);
+}
+
+RNNTStatus mrnnt_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out_dev, int64_t out_stride,
+                       float *costs_dev, hipStream_t stream) {
+    return align_impl(p, ws, ws_bytes, alignment_out_dev, out_stride, costs_dev, stream, false);
+}
+
+RNNTStatus mrnnt_hat_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out_dev,
+                           int64_t out_stride, float *costs_dev, hipStream_t stream) {
+    return align_impl(p, ws, ws_bytes, alignment_out_dev, out_stride, costs_dev, stream, true);
 }
 
 RNNTStatus mrnnt_posteriors(const mrnnt_problem *p, const void *ws, float *blank_post_dev, float *label_post_dev,

@@ -83,6 +83,30 @@ static inline __attribute__((always_inline)) void row_max_sum_body(const float *
     sum_out = sum;
 }
 
+// The same over the row without element `skip` (the factorised blank, hat_row): max and sum_{v != skip} e^(z_v - max),
+// the exps against 0 where every other element is -inf (sum 0, not e^(-inf + inf)); NaN poisons the sum as above.
+static inline __attribute__((always_inline)) void row_max_sum_skip_body(const float *__restrict__ z, int V, int skip,
+                                                                        float &m_out, double &sum_out) {
+    constexpr float ninf = -std::numeric_limits<float>::infinity();
+    float m = ninf;
+#pragma omp simd reduction(max : m)
+    for (int v = 0; v < V; ++v) {
+        const float x = v == skip ? ninf : z[v];
+        m = x > m ? x : m;
+    }
+    const float mr = m == ninf ? 0.0f : m;
+    double sum = 0.0;
+    for (int v0 = 0; v0 < V; v0 += kBlock) {
+        const int v1 = std::min(V, v0 + kBlock);
+        float s = 0.0f;
+#pragma omp simd reduction(+ : s)
+        for (int v = v0; v < v1; ++v) s += v == skip ? 0.0f : vexp(z[v] - mr);
+        sum += (double)s;
+    }
+    m_out = m;
+    sum_out = sum;
+}
+
 // g_v = e^(z_v + c) * sc (g may be z itself: element-wise, each element read before it is written)
 static inline __attribute__((always_inline)) void grad_row_body(const float *z, float *g, int V, float c, float sc) {
 #pragma omp simd
@@ -98,6 +122,17 @@ __attribute__((target("avx2,fma"))) void row_max_sum(const float *z, int V, floa
 __attribute__((target("avx512f,avx512dq,avx512bw,avx512vl,fma"))) void row_max_sum(const float *z, int V, float &m,
                                                                                     double &s) {
     row_max_sum_body(z, V, m, s);
+}
+
+__attribute__((target("default"))) void row_max_sum_skip(const float *z, int V, int skip, float &m, double &s) {
+    row_max_sum_skip_body(z, V, skip, m, s);
+}
+__attribute__((target("avx2,fma"))) void row_max_sum_skip(const float *z, int V, int skip, float &m, double &s) {
+    row_max_sum_skip_body(z, V, skip, m, s);
+}
+__attribute__((target("avx512f,avx512dq,avx512bw,avx512vl,fma"))) void row_max_sum_skip(const float *z, int V, int skip,
+                                                                                         float &m, double &s) {
+    row_max_sum_skip_body(z, V, skip, m, s);
 }
 
 __attribute__((target("default"))) void grad_row(const float *z, float *g, int V, float c, float sc) {
@@ -302,7 +337,31 @@ inline void row_window(const CpuPlan &pl, const Views &w, int64_t c, int t, int 
     hi = std::min(hi, whi);
 }
 
-void softmax_pass(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int nt) {
+// log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)): -inf -> -inf, +inf -> 0, NaN -> NaN
+inline double log_sigmoid(double z) { return std::fmin(z, 0.0) - std::log1p(std::exp(-std::fabs(z))); }
+
+// The factorised-blank row (mrnnt_cpu_hat_*; the HIP path's HAT bodies and hat_lp, mrnnt_lsm.h): blank a Bernoulli on
+// its own logit, the labels a softmax over the other V - 1 logits -- den' = -LSE_{v != blank} from one reduce of the
+// row that skips z_blank (it never enters a max or a sum),
+//   lpb = log sigmoid(z_b),   lpe = log sigmoid(-z_b) + z_l + den'   (a label equal to blank: no such arc).
+// A NaN or +inf logit anywhere in the row makes both NaN (z_b = +inf included), as the standard row. A masked (-inf)
+// label logit, and a row whose non-blank logits are all masked (den' = +inf), have no label arc: lpe = -inf.
+void hat_row(const float *z, int V, int blank, int label, float *den_out, double *lpb, double *lpe) {
+    float m;
+    double sum;
+    row_max_sum_skip(z, V, blank, m, sum);
+    const double den = -(double)m - std::log(sum);
+    const double zb = z[blank];
+    const bool bad = zb == std::numeric_limits<double>::infinity() || den != den;
+    const double ze = label < 0 ? 0.0 : (label == blank ? kNegInf : (double)z[label]);
+    constexpr double nan = std::numeric_limits<double>::quiet_NaN();
+    *den_out = (float)den;
+    *lpb = bad ? nan : log_sigmoid(zb);
+    const bool none = ze == kNegInf || den == -kNegInf;
+    *lpe = bad ? nan : (none ? kNegInf : log_sigmoid(-zb) + (ze + den));
+}
+
+void softmax_pass(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int nt, bool hat = false) {
     const float *acts = static_cast<const float *>(p->acts);
     const int V = pl.V;
 #pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
@@ -324,6 +383,10 @@ void softmax_pass(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int
                 continue;
             }
             const float *z = acts + (a0 + s) * V;
+            if (hat) {
+                hat_row(z, V, p->blank, s < S ? lab[s] : -1, &w.den[r], &w.lpb[r], &w.lpe[r]);
+                continue;
+            }
             float m;
             double sum;
             row_max_sum(z, V, m, sum);
@@ -497,6 +560,58 @@ void grad_column(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, cons
     }
 }
 
+// Factorised-blank gradient of one lattice column (mrnnt_cpu_hat_backward; the HIP path's HatRows, mrnnt_hat.hip):
+// with cb / ce the blank / label arc posteriors of the row,
+//   g[blank] = ce sigmoid(z_b) - cb sigmoid(-z_b),   g[v != blank] = ce (e^(z_v + den') - [v == label(s)]),
+// times grad_scale[b], each sigmoid from lpb = log sigmoid(z_b) by itself (sigmoid(-z_b) = -expm1(lpb)). A row whose ce
+// and blank element are both zero in fp32 is stored as exact zeros without reading acts; out-of-band rows as
+// grad_column stores them.
+void grad_column_hat(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, const float *scale, float *grads,
+                     int b, int t) {
+    const int T = p->T_host[b], S = p->S_host[b], W = S + 1, V = pl.V, blank = p->blank;
+    const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+    const float *acts = static_cast<const float *>(p->acts);
+    const float sc = scale ? scale[p->grad_scale_broadcast ? 0 : b] : 1.0f;
+    const double ll = w.ll[b];
+    const float zero = (ll > kNegInf ? 0.0f : std::numeric_limits<float>::quiet_NaN()) * sc;
+    const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
+    const double *A = w.alpha + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
+    const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
+    for (int s = 0; s < W; ++s) {
+        float *g = grads + (a0 + s) * V;
+        if (s < lo || s > hi) {
+            std::fill(g, g + V, zero);
+            continue;
+        }
+        const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s];
+        const double b1 = (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s];
+        const double b2 =
+            (s == S) ? kNegInf : ((t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1]);
+        const double base = am - ll;
+        const int64_t r = r0 + s;
+        const double q = w.lpb[r];
+        const double le = w.lpe[r] + base + b2;
+        const float cb = (float)std::exp(q + base + b1);
+        const float ce = s < S ? (float)std::exp(le) : 0.0f;
+        const float gb = (float)((double)ce * std::exp(q) - (double)cb * -std::expm1(q));
+        if (ce == 0.0f && gb == 0.0f) {
+            std::fill(g, g + V, zero);
+            continue;
+        }
+        const float *z = acts + (a0 + s) * V;
+        const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != blank) ? lab[s] : -1;
+        const float zl = l >= 0 ? z[l] : 0.0f;  // read first: grads may alias acts
+        if (ce != 0.0f) {  // (ce = 0: no label arc, every non-blank element is 0 -- s = S, or every label masked)
+            const float c = (float)((double)w.den[r] + le);
+            grad_row(z, g, V, c, sc);
+            if (l >= 0) g[l] = (vexp(zl + c) - ce) * sc;
+        } else {
+            std::fill(g, g + V, 0.0f * sc);
+        }
+        g[blank] = gb * sc;
+    }
+}
+
 // Arc posteriors of row (t, s) inside the monotonic band (mrnnt_cpu_posteriors; the HIP path's row_post,
 // mrnnt_posterior.hip): the blank and label corrections of grad_column in fp64,
 //   bp = e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll),  ep = e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll)  (0 at s = S).
@@ -535,8 +650,8 @@ RNNTStatus mrnnt_cpu_workspace_size(const mrnnt_problem *p, size_t *bytes) {
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs, int with_beta,
-                             int num_threads) {
+static RNNTStatus cpu_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs, int with_beta,
+                                   int num_threads, bool hat) {
     CpuPlan pl;
     RNNTStatus st = make_cpu_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -546,7 +661,7 @@ RNNTStatus mrnnt_cpu_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, 
     const Views w = views(pl, ws);
     const int nt = threads_of(num_threads);
     if (pl.align) build_band(p, pl, w, nt);
-    softmax_pass(p, pl, w, nt);
+    softmax_pass(p, pl, w, nt, hat);
     const int dirs = with_beta ? 2 : 1;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
     for (int i = 0; i < pl.B * dirs; ++i) {
@@ -563,8 +678,18 @@ RNNTStatus mrnnt_cpu_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, 
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out, int64_t out_stride,
-                           float *costs, int num_threads) {
+RNNTStatus mrnnt_cpu_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs, int with_beta,
+                             int num_threads) {
+    return cpu_forward_impl(p, ws, ws_bytes, costs, with_beta, num_threads, false);
+}
+
+RNNTStatus mrnnt_cpu_hat_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs, int with_beta,
+                                 int num_threads) {
+    return cpu_forward_impl(p, ws, ws_bytes, costs, with_beta, num_threads, true);
+}
+
+static RNNTStatus cpu_align_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out,
+                                 int64_t out_stride, float *costs, int num_threads, bool hat) {
     CpuPlan pl;
     RNNTStatus st = make_cpu_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -579,7 +704,7 @@ RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, in
     const int nt = threads_of(num_threads);
     // p->alignment may be alignment_out itself: the band is built from it before any row is written
     if (pl.align) build_band(p, pl, w, nt);
-    softmax_pass(p, pl, w, nt);
+    softmax_pass(p, pl, w, nt, hat);
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
     for (int b = 0; b < pl.B; ++b) {
         const double fin = viterbi_utt(p, pl, w, b, alignment_out + (int64_t)b * out_stride, out_stride);
@@ -588,8 +713,18 @@ RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, in
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, float *grads,
-                              int num_threads) {
+RNNTStatus mrnnt_cpu_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out, int64_t out_stride,
+                           float *costs, int num_threads) {
+    return cpu_align_impl(p, ws, ws_bytes, alignment_out, out_stride, costs, num_threads, false);
+}
+
+RNNTStatus mrnnt_cpu_hat_align(const mrnnt_problem *p, void *ws, size_t ws_bytes, int *alignment_out,
+                               int64_t out_stride, float *costs, int num_threads) {
+    return cpu_align_impl(p, ws, ws_bytes, alignment_out, out_stride, costs, num_threads, true);
+}
+
+static RNNTStatus cpu_backward_impl(const mrnnt_problem *p, const void *ws, const float *grad_scale, float *grads,
+                                    int num_threads, bool hat) {
     CpuPlan pl;
     RNNTStatus st = make_cpu_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -601,10 +736,21 @@ RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *ws, const floa
 #pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
     for (int64_t c = 0; c < pl.cols; ++c) {
         const int b = col_utt(pl, c);
-        grad_column(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
+        if (hat) grad_column_hat(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
+        else grad_column(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
     }
     zero_padding_rows(p, pl, grads, pl.V, nt);
     return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, float *grads,
+                              int num_threads) {
+    return cpu_backward_impl(p, ws, grad_scale, grads, num_threads, false);
+}
+
+RNNTStatus mrnnt_cpu_hat_backward(const mrnnt_problem *p, const void *ws, const float *grad_scale, float *grads,
+                                  int num_threads) {
+    return cpu_backward_impl(p, ws, grad_scale, grads, num_threads, true);
 }
 
 RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *blank_post, float *label_post, float *emit,

@@ -1,6 +1,6 @@
 // mrnnt_grad.h -- the dense logit-gradient streamers and their launch ladder, over a compile-time row policy P: the
-// loss gradient (LossRows, mrnnt_grad.hip), the path-score gradient (PathRows, mrnnt_path.hip) and the expected-cost
-// gradient (ExpectRows, mrnnt_expect.hip). P supplies
+// loss gradient (LossRows, mrnnt_grad.hip), the path-score gradient (PathRows, mrnnt_path.hip), the expected-cost
+// gradient (ExpectRows, mrnnt_expect.hip) and the factorised-blank loss gradient (HatRows, mrnnt_hat.hip). P supplies
 //   Col, column()   what a lattice column sets up once: its band of rows with a gradient; zero(): the other rows' value
 //   Slot, stage()   a row's coefficients as they are staged in LDS, two buffers of 256 slots (a dead slot: the row is
 //                   stored as zero()), live(); skip() / skipped(): a dead slot whose row already holds zero() (row state)

@@ -80,6 +80,9 @@ struct DevProblem {
     double *ex_A = nullptr, *ex_Bk = nullptr, *ex_R = nullptr;
     const float *ex_wb = nullptr, *ex_we = nullptr;
     const float *ex_ge = nullptr, *ex_gc = nullptr;
+    // mrnnt_hat_* (factorised blank): the log-softmax launch takes the kernels whose rows keep the blank logit out of
+    // the denominator (launch_softmax dispatches on it on the host; no kernel reads it)
+    int hat = 0;
 };
 
 // rows of the caller's grads buffer a gradient launch covers (host bound)
@@ -380,6 +383,10 @@ int joint_reduce_trace(unsigned long long *out, int n);  // development build: t
 hipError_t launch_chase(const DevProblem &p, const ChaseArgs &c, int elem, int S_max, int with_beta, int producers,
                         float *costs, hipStream_t stream);
 hipError_t launch_grad(const DevProblem &p, int elem, const float *scale, void *grads, int grid, hipStream_t stream);
+// mrnnt_hat_backward (mrnnt_hat.hip): the factorised-blank gradient over the row policy HatRows, after a forward with
+// p.hat on the same workspace (den = -LSE over the non-blank logits, lp.b = log sigmoid(z_blank))
+hipError_t launch_hat_grad(const DevProblem &p, int elem, const float *scale, void *grads, int grid,
+                           hipStream_t stream);
 hipError_t launch_count_live(const DevProblem &p, unsigned long long *count, hipStream_t stream);
 hipError_t launch_pad_zero(const DevProblem &p, int elem, void *grads, hipStream_t stream);
 hipError_t launch_fill_zero(void *dst, size_t bytes, int grid_max, hipStream_t stream);

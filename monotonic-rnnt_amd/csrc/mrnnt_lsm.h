@@ -58,6 +58,58 @@ __device__ __forceinline__ float lane_pick(const float (&x)[N], int k) {
     return v[k];
 }
 
+// ---- the factorised-blank flavour (HAT = true; mrnnt_hat_*, DESIGN.md "Factorised blank") ----
+// blank is a Bernoulli on its own logit and the labels a softmax over the other V - 1:
+//   lpb = log sigmoid(z_b),   lpe = log sigmoid(-z_b) + z_l - LSE_{v != b} z_v,   den' = -LSE_{v != b} z_v.
+// The bodies below keep z_b out of the max and the sum by overwriting it with -inf in the lane that holds it, after
+// z_b has been picked (subtracting exp(z_b - M) from the whole row's sum instead cancels to nothing when the blank
+// logit dominates the row), and hand (z_b, z_l, den') to hat_lp.
+
+// x[k] = val in this lane only (k wave-uniform: one indexed register move under the lane's exec bit)
+template <int N>
+__device__ __forceinline__ void lane_put(float (&x)[N], int k, float val) {
+    typedef float VN __attribute__((ext_vector_type(N)));
+    VN v;
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = x[i];
+    v[k] = val;
+#pragma unroll
+    for (int i = 0; i < N; ++i) x[i] = v[i];
+}
+
+// log sigmoid(z) = min(z, 0) - log1p(exp(-|z|)), the bounded correction (in [0, ln 2]) on the fp32 hardware exp2 / log2
+// with the log1p rounding fix (log(u) * e / (u - 1), u = 1 + e: relative error ~1e-7 of the correction, so
+// log sigmoid(+60) = -e^-60 keeps its digits), assembled in fp64 -- the form of lse2 and of den. -inf -> -inf,
+// +inf -> 0, NaN -> NaN.
+__device__ __forceinline__ double log_sigmoid(float z) {
+    const float e = fast_exp2(-fabsf(z) * kLog2e);
+    const float u = 1.0f + e;
+    const float c = (u == 1.0f) ? e : fast_log2(u) * kLn2 * (e / (u - 1.0f));
+    return (double)fminf(z, 0.0f) - (double)c;
+}
+
+// The two log-probs of a factorised row from its blank logit, its label logit (0 at s == S; -inf: no such arc) and
+// den' (fp64). A row the standard loss would make NaN -- a NaN or +inf logit anywhere in it -- is NaN in both, so the
+// utterance's cost is NaN whichever arc its paths take: z_b = NaN and a NaN / +inf label logit (den' = NaN) do that by
+// themselves in lpe, and z_b = +inf (log sigmoid = 0: a certain blank) is made NaN here like any other +inf logit.
+// A masked label logit (-inf), and a row whose non-blank logits are all masked (den' = +inf; V = 1 is such a row), have
+// no label arc: lpe = -inf, not -inf + inf.
+__device__ __forceinline__ Lp hat_lp(float zb, float ze, double den) {
+    const bool bad = zb == __builtin_huge_valf() || den != den;
+    const bool none = ze == NEG_INF_F || den == __builtin_huge_val();
+    const double nan = __builtin_nan("");
+    return Lp{bad ? nan : log_sigmoid(zb), bad ? nan : (none ? NEG_INF_D : log_sigmoid(-zb) + ((double)ze + den))};
+}
+
+// the label of a factorised row: a label equal to blank is no label arc (its logit is not among the V - 1)
+__device__ __forceinline__ int hat_label(int lab, int blank, float &ze) {
+    if (lab == blank) {
+        ze = NEG_INF_F;
+        return -1;
+    }
+    return lab;
+}
+
 // Lean kernel (softmax_variant 13, the default; 14 / 15 select R = 1 / 4 rows per wave): the same
 // column walk and online per-lane (max, sum) as softmax_kernel, with the per-row overhead taken off the
 // vector pipe -- (max, sum) merged by DPP reductions into wave-uniform scalars (no ds_bpermute butterfly, one
@@ -70,7 +122,8 @@ __device__ __forceinline__ float lane_pick(const float (&x)[N], int k) {
 // NWV / wv / [rlo, rhi]: the waves sharing the column, this wave's index among them and the rows to produce (the
 // producers: 4 waves, every row; the chase launch's self-help: one wave, the rows its recursion lanes read). A row's
 // value does not depend on which rows share its pass, so every split produces the same bits.
-template <class IO, int U, int R, bool NTL, bool FULL, bool ONE, bool WT, int NWV = 4>
+// HAT: the factorised-blank flavour (above) -- the blank element masked in its lane before the max, hat_lp at the end.
+template <class IO, int U, int R, bool NTL, bool FULL, bool ONE, bool WT, int NWV = 4, bool HAT = false>
 __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k, int wv = -1, int rlo = 0,
                                             int rhi = 1 << 30) {
     constexpr int E = IO::E;
@@ -109,8 +162,8 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const bool has = r < nrow && s + r < S;
-                const int lab = checked_label(has, has ? __builtin_amdgcn_readfirstlane(lab_b[s + r]) : 0, p.V,
-                                              ze[r]);
+                int lab = checked_label(has, has ? __builtin_amdgcn_readfirstlane(lab_b[s + r]) : 0, p.V, ze[r]);
+                if constexpr (HAT) lab = hat_label(lab, blank, ze[r]);
                 float cm = NEG_INF_F;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -119,12 +172,17 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
 #pragma unroll
                     for (int i = 0; i < E; ++i) {
                         xf[r][u * E + i] = t4[i];
-                        cm = fmaxf(cm, t4[i]);
+                        if constexpr (!HAT) cm = fmaxf(cm, t4[i]);
                     }
                 }
                 const int jb = blank / E;
                 zb[r] = __int_as_float(__builtin_amdgcn_readlane(
                     __float_as_int(lane_pick<U * E>(xf[r], (jb >> 6) * E + blank % E)), jb & 63));
+                if constexpr (HAT) {  // z_b picked: out of the row, in the lane that holds it, before the max
+                    if (lane == (jb & 63)) lane_put<U * E>(xf[r], (jb >> 6) * E + blank % E, NEG_INF_F);
+#pragma unroll
+                    for (int k = 0; k < U * E; ++k) cm = fmaxf(cm, xf[r][k]);
+                }
                 if (lab >= 0) {
                     const int je = lab / E;
                     ze[r] = __int_as_float(__builtin_amdgcn_readlane(
@@ -152,7 +210,8 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
                 const int64_t row = rowc + s + lane;
                 const double den = -(double)em - log_row_sum(es);
                 p.den[row] = (float)den;
-                st_lp<WT>(p, row, Lp{(double)ezb + den, (double)eze + den});
+                if constexpr (HAT) st_lp<WT>(p, row, hat_lp(ezb, eze, den));
+                else st_lp<WT>(p, row, Lp{(double)ezb + den, (double)eze + den});
             }
         }
         return;  // next column
@@ -165,6 +224,7 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
         for (int r = 0; r < R; ++r) {
             const bool has = r < nrow && s + r < S;
             lab[r] = checked_label(has, has ? __builtin_amdgcn_readfirstlane(lab_b[s + r]) : 0, p.V, ze[r]);
+            if constexpr (HAT) lab[r] = hat_label(lab[r], blank, ze[r]);
             m[r] = NEG_INF_F;
             sum[r] = 0.0f;
             zb[r] = 0.0f;
@@ -195,7 +255,7 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
 #pragma unroll
                     for (int i = 0; i < E; ++i) {
                         xf[u * E + i] = t4[i];
-                        cm = fmaxf(cm, t4[i]);
+                        if constexpr (!HAT) cm = fmaxf(cm, t4[i]);
                     }
                 }
                 // blank / label logits: uniform position inside this chunk -> indexed move + readlane
@@ -203,6 +263,12 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
                 if (jb >= 0 && jb < CH) {
                     const float v = lane_pick<U * E>(xf, (jb >> 6) * E + blank % E);
                     zb[r] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), jb & 63));
+                    if constexpr (HAT)  // the chunk that holds z_b: out of the row before this chunk's max
+                        if (lane == (jb & 63)) lane_put<U * E>(xf, (jb >> 6) * E + blank % E, NEG_INF_F);
+                }
+                if constexpr (HAT) {
+#pragma unroll
+                    for (int k = 0; k < U * E; ++k) cm = fmaxf(cm, xf[k]);
                 }
                 const int je = lab[r] >= 0 ? lab[r] / E - base : -1;
                 if (je >= 0 && je < CH) {
@@ -240,7 +306,8 @@ __device__ __forceinline__ void lean_column(const DevProblem &p, const ColRef &k
             const int64_t row = rowc + s + lane;
             const double den = -(double)em - log_row_sum(es);
             p.den[row] = (float)den;
-            st_lp<WT>(p, row, Lp{(double)ezb + den, (double)eze + den});
+            if constexpr (HAT) st_lp<WT>(p, row, hat_lp(ezb, eze, den));
+            else st_lp<WT>(p, row, Lp{(double)ezb + den, (double)eze + den});
         }
     }
 }
@@ -257,7 +324,7 @@ __device__ __forceinline__ float dpp16(float v) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
-template <class IO, int NR, bool NTL, bool WT, int NWV = 4>
+template <class IO, int NR, bool NTL, bool WT, int NWV = 4, bool HAT = false>
 __device__ __forceinline__ void row16_column(const DevProblem &p, const ColRef &k, int wv = -1, int rlo = 0,
                                              int rhi = 1 << 30) {
     constexpr int E = IO::E;
@@ -303,7 +370,8 @@ __device__ __forceinline__ void row16_column(const DevProblem &p, const ColRef &
                 const int64_t ae = (arow + s) * (int64_t)p.V;
                 zb[r] = IO::to_f(as[ae + blank]);
                 const bool has = s < S;
-                const int lab = checked_label(has, has ? lab_b[s] : 0, p.V, ze[r]);
+                int lab = checked_label(has, has ? lab_b[s] : 0, p.V, ze[r]);
+                if constexpr (HAT) lab = hat_label(lab, blank, ze[r]);
                 if (lab >= 0) ze[r] = IO::to_f(as[ae + lab]);
             }
         }
@@ -318,8 +386,14 @@ __device__ __forceinline__ void row16_column(const DevProblem &p, const ColRef &
 #pragma unroll
                 for (int i = 0; i < E; ++i) {
                     xf[u * E + i] = t4[i];
-                    m = fmaxf(m, t4[i]);
+                    if constexpr (!HAT) m = fmaxf(m, t4[i]);
                 }
+            }
+            if constexpr (HAT) {  // z_b (loaded with the row, above): out of the row, in the lane that holds it
+                const int jb = blank / E;
+                if (l16 == (jb & 15)) lane_put<4 * E>(xf, (jb >> 4) * E + blank % E, NEG_INF_F);
+#pragma unroll
+                for (int k = 0; k < 4 * E; ++k) m = fmaxf(m, xf[k]);
             }
             m = fmaxf(m, dpp16<0xB1>(m));   // quad_perm [1,0,3,2]
             m = fmaxf(m, dpp16<0x4E>(m));   // quad_perm [2,3,0,1]
@@ -337,7 +411,8 @@ __device__ __forceinline__ void row16_column(const DevProblem &p, const ColRef &
                 const int64_t row = rowc + s0 + 4 * r + g;
                 const double den = -(double)m - log_row_sum(acc);
                 p.den[row] = (float)den;
-                st_lp<WT>(p, row, Lp{(double)zb[r] + den, (double)ze[r] + den});
+                if constexpr (HAT) st_lp<WT>(p, row, hat_lp(zb[r], ze[r], den));
+                else st_lp<WT>(p, row, Lp{(double)zb[r] + den, (double)ze[r] + den});
             }
         }
     }

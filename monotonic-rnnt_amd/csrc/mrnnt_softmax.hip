@@ -103,22 +103,23 @@ __global__ __launch_bounds__(256) void softmax_kernel(DevProblem p) {
     });
 }
 
-template <class IO, int U, int R, bool NTL, bool FULL, bool ONE = false>
+// HAT (here and below): the factorised-blank flavour of the body (mrnnt_lsm.h), a kernel of its own per flavour
+template <class IO, int U, int R, bool NTL, bool FULL, bool ONE = false, bool HAT = false>
 __global__ __launch_bounds__(256) void softmax_lean_kernel(DevProblem p) {
     resolve_dyn(p);
     zero_lp_pads(p);
-    walk_columns(p, [&](const ColRef &k) { lean_column<IO, U, R, NTL, FULL, ONE, false>(p, k); });
+    walk_columns(p, [&](const ColRef &k) { lean_column<IO, U, R, NTL, FULL, ONE, false, 4, HAT>(p, k); });
 }
 
-template <class IO, int NR, bool NTL>
+template <class IO, int NR, bool NTL, bool HAT = false>
 __global__ __launch_bounds__(256) void softmax_row16_kernel(DevProblem p) {
     resolve_dyn(p);
     zero_lp_pads(p);
-    walk_columns(p, [&](const ColRef &k) { row16_column<IO, NR, NTL, false>(p, k); });
+    walk_columns(p, [&](const ColRef &k) { row16_column<IO, NR, NTL, false, 4, HAT>(p, k); });
 }
 
 // Scalar path (any V, any alignment, any element type): one row per wave, lanes stride over v.
-template <class IO>
+template <class IO, bool HAT = false>
 __global__ __launch_bounds__(256) void softmax_scalar_kernel(DevProblem p) {
     resolve_dyn(p);
     zero_lp_pads(p);
@@ -139,7 +140,8 @@ __global__ __launch_bounds__(256) void softmax_scalar_kernel(DevProblem p) {
         zero_fill_outside_band<false>(p, rowc, S, lo, hi);
         for (int s = lo + wave; s <= hi; s += 4) {
             float ze;
-            const int lab = checked_label(s < S, s < S ? lab_b[s] : 0, V, ze);
+            int lab = checked_label(s < S, s < S ? lab_b[s] : 0, V, ze);
+            if constexpr (HAT) lab = hat_label(lab, blank, ze);
             const Sc *__restrict__ z = acts + (arow + s) * (int64_t)V;
             float m = NEG_INF_F, sum = 0.0f, zb = 0.0f;
             for (int v0 = 0; v0 < V; v0 += 256) {
@@ -148,7 +150,10 @@ __global__ __launch_bounds__(256) void softmax_scalar_kernel(DevProblem p) {
                 for (int u = 0; u < 4; ++u) {
                     const int v = v0 + lane + 64 * u;
                     x[u] = v < V ? IO::to_f(z[v]) : NEG_INF_F;
-                    if (v == blank) zb = x[u];
+                    if (v == blank) {
+                        zb = x[u];
+                        if constexpr (HAT) x[u] = NEG_INF_F;  // z_b picked: out of the row before the max and the sum
+                    }
                     if (v == lab) ze = x[u];
                 }
                 const float mn = fmaxf(m, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
@@ -162,7 +167,15 @@ __global__ __launch_bounds__(256) void softmax_scalar_kernel(DevProblem p) {
             wave_reduce_max_sum(m, sum);
             const float zbv = __shfl(zb, blank & 63);
             const float zev = lab >= 0 ? __shfl(ze, lab & 63) : ze;  // ze: 0, or NaN (bad label)
-            if (lane == 0) write_row(p, rowc + s, m, sum, zbv, zev);
+            if constexpr (HAT) {
+                if (lane == 0) {
+                    const double den = -(double)m - log_row_sum(sum);
+                    p.den[rowc + s] = (float)den;
+                    p.lp[rowc + s] = hat_lp(zbv, zev, den);
+                }
+            } else if (lane == 0) {
+                write_row(p, rowc + s, m, sum, zbv, zev);
+            }
         }
     });
 }
@@ -223,9 +236,45 @@ static void launch_vec(const DevProblem &p, int grid, hipStream_t stream) {
     else launch_u<IO, NTL, 1>(p, grid, stream);
 }
 
+// The factorised-blank launch (p.hat): the default ladder above with the HAT bodies, in either build (the
+// development build's variants are the standard loss's).
+template <class IO, bool NTL, int U>
+static void launch_hat_u(const DevProblem &p, int grid, hipStream_t stream) {
+    const int VL = p.V / IO::E;
+    const bool full = VL % (64 * U) == 0;
+    constexpr int RD = U == 1 ? 4 : 2;
+    if (VL <= 64)
+        softmax_row16_kernel<IO, 1, NTL, true><<<grid, 256, 0, stream>>>(p);
+    else if (VL <= 64 * U && full)
+        softmax_lean_kernel<IO, U, RD, NTL, true, true, true><<<grid, 256, 0, stream>>>(p);
+    else if (VL <= 64 * U)
+        softmax_lean_kernel<IO, U, RD, NTL, false, true, true><<<grid, 256, 0, stream>>>(p);
+    else if (full)
+        softmax_lean_kernel<IO, U, RD, NTL, true, false, true><<<grid, 256, 0, stream>>>(p);
+    else
+        softmax_lean_kernel<IO, U, RD, NTL, false, false, true><<<grid, 256, 0, stream>>>(p);
+}
+
+template <class IO, bool NTL>
+static void launch_hat_vec(const DevProblem &p, int grid, hipStream_t stream) {
+    const int VL = p.V / IO::E;
+    if (VL >= 192) launch_hat_u<IO, NTL, 4>(p, grid, stream);
+    else if (VL >= 96) launch_hat_u<IO, NTL, 2>(p, grid, stream);
+    else launch_hat_u<IO, NTL, 1>(p, grid, stream);
+}
+
 template <class IO>
 static void launch_io(const DevProblem &p, int grid, hipStream_t stream) {
     const bool vec = (p.V % IO::E) == 0 && (reinterpret_cast<uintptr_t>(p.acts) % 16) == 0;
+    if (p.hat) {
+        if (!vec)
+            softmax_scalar_kernel<IO, true><<<grid, 256, 0, stream>>>(p);
+        else if (nt_acts_loads(p, sizeof(typename IO::S)))
+            launch_hat_vec<IO, true>(p, grid, stream);
+        else
+            launch_hat_vec<IO, false>(p, grid, stream);
+        return;
+    }
     if (!vec)
         softmax_scalar_kernel<IO><<<grid, 256, 0, stream>>>(p);
     else if (nt_acts_loads(p, sizeof(typename IO::S)))

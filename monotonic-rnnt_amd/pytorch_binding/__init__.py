@@ -4,9 +4,10 @@ from .monotonic_rnnt_joint import (MonotonicRNNTJointExpectedCostFunction, Monot
                                    monotonic_rnnt_joint_expected_cost, monotonic_rnnt_joint_loss,
                                    monotonic_rnnt_joint_path_loss, monotonic_rnnt_joint_posteriors,
                                    monotonic_rnnt_joint_sample)
-from .monotonic_rnnt_op import (MonotonicRNNTExpectedCostFunction, MonotonicRNNTFunction, MonotonicRNNTLoss,
-                                MonotonicRNNTPathFunction, monotonic_rnnt_align, monotonic_rnnt_cpp,
-                                monotonic_rnnt_expected_cost, monotonic_rnnt_loss, monotonic_rnnt_path_loss,
+from .monotonic_rnnt_op import (MonotonicRNNTExpectedCostFunction, MonotonicRNNTFunction, MonotonicRNNTHatFunction,
+                                MonotonicRNNTHatLoss, MonotonicRNNTLoss, MonotonicRNNTPathFunction,
+                                monotonic_rnnt_align, monotonic_rnnt_cpp, monotonic_rnnt_expected_cost,
+                                monotonic_rnnt_hat_loss, monotonic_rnnt_loss, monotonic_rnnt_path_loss,
                                 monotonic_rnnt_posteriors, monotonic_rnnt_sample)
 
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp",
@@ -15,4 +16,5 @@ __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", 
            "monotonic_rnnt_sample", "monotonic_rnnt_joint_sample", "MonotonicRNNTPathFunction",
            "monotonic_rnnt_path_loss", "MonotonicRNNTJointPathFunction", "monotonic_rnnt_joint_path_loss",
            "MonotonicRNNTExpectedCostFunction", "monotonic_rnnt_expected_cost",
-           "MonotonicRNNTJointExpectedCostFunction", "monotonic_rnnt_joint_expected_cost"]
+           "MonotonicRNNTJointExpectedCostFunction", "monotonic_rnnt_joint_expected_cost",
+           "MonotonicRNNTHatFunction", "monotonic_rnnt_hat_loss", "MonotonicRNNTHatLoss"]

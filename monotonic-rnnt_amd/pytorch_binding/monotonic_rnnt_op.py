@@ -349,15 +349,17 @@ def _call(prep: _Prepared, name: str, *args, pending: bool = False, lengths: boo
             check_lengths(sync=False)
 
 
-def _forward(prep: _Prepared, with_beta: bool):
+def _forward(prep: _Prepared, with_beta: bool, hat: bool = False):
+    """The forward on a fresh workspace; hat: the factorised-blank entry points (mrnnt_hat_* / mrnnt_cpu_hat_*)."""
     ws = prep.workspace()
     costs = torch.empty(prep.problem.B, dtype=torch.float32, device=prep.device)
-    _call(prep, "forward", _ptr(ws), ws.numel(), _ptr(costs), 1 if with_beta else 0, pending=True)
+    _call(prep, "hat_forward" if hat else "forward", _ptr(ws), ws.numel(), _ptr(costs), 1 if with_beta else 0,
+          pending=True)
     return costs, ws
 
 
 def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tensor],
-              grads: Optional[torch.Tensor] = None) -> torch.Tensor:
+              grads: Optional[torch.Tensor] = None, hat: bool = False) -> torch.Tensor:
     ticket = None
     if grads is None:  # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), with the
         # state of its rows: the tracked entry does not store again the zero rows the buffer already holds
@@ -373,11 +375,11 @@ def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tens
         else:
             grad_scale = grad_scale.to(prep.device, torch.float32).contiguous()
     if ticket is not None:
-        _call(prep, "backward_tracked", _ptr(ws), _ptr(grad_scale), _ptr(grads), _ptr(ticket.state),
-              ticket.state.numel(), lengths=False)
+        _call(prep, "hat_backward_tracked" if hat else "backward_tracked", _ptr(ws), _ptr(grad_scale), _ptr(grads),
+              _ptr(ticket.state), ticket.state.numel(), lengths=False)
         ticket.commit()  # enqueued: the state describes the buffer from here on (in stream order)
     else:
-        _call(prep, "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
+        _call(prep, "hat_backward" if hat else "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
     return grads
 
 
@@ -433,6 +435,58 @@ def monotonic_rnnt_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths:
     return result
 
 
+class MonotonicRNNTHatFunction(torch.autograd.Function):
+    """The loss with the factorised blank of the hybrid autoregressive transducer (mrnnt_hat_forward /
+    mrnnt_hat_backward and the mrnnt_cpu_hat_* twins, include/mrnnt.h): apply(acts, labels, input_lengths,
+    label_lengths, alignment=None, max_distance_from_alignment=0, blank_label=0) -> costs [B]."""
+
+    @staticmethod
+    def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
+                max_distance_from_alignment: int = 0, blank_label: int = 0) -> torch.Tensor:
+        prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
+                         blank_label)
+        need_grad = bool(ctx.needs_input_grad[0])
+        costs, ws = _forward(prep, with_beta=need_grad, hat=True)
+        if need_grad:  # (acts and the workspace: as MonotonicRNNTFunction)
+            ctx.save_for_backward(acts, ws)
+            ctx.prep = prep
+        return costs
+
+    @staticmethod
+    def backward(ctx, grad_outputs):
+        _, ws = ctx.saved_tensors
+        grads = _backward(ctx.prep, ws, grad_outputs, hat=True)
+        return grads, None, None, None, None, None, None
+
+
+def monotonic_rnnt_hat_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                            label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
+                            max_distance_from_alignment: int = 0, blank_label: int = 0) -> torch.Tensor:
+    """The monotonic RNN-T loss with the factorised blank of the hybrid autoregressive transducer (HAT): for a row z
+    of logits, blank is a Bernoulli on its own logit and the labels a softmax over the other V - 1 logits,
+
+        log p(blank) = log sigmoid(z[blank])
+        log p(label) = log sigmoid(-z[blank]) + z[label] - logsumexp(z[v] for v != blank)
+
+    -- the form that makes internal-LM subtraction well defined and separates the emission decision from the label
+    identity. Lattice, band, alignment restriction, recursion and cost are monotonic_rnnt_loss's, and so are the
+    arguments and everything they support: CPU and GPU tensors, bfloat16 / float16 acts, the padded 4-D layout,
+    GPU-resident lengths without a host read, HIP-graph capture. blank_label may be any index in [0, V).
+
+    The transform runs inside the log-softmax and gradient kernels (no second N x V tensor; the step moves the bytes
+    of monotonic_rnnt_loss) with the blank logit kept out of the denominator's max and sum, so a dominant or
+    suppressed blank logit loses no digits. A -inf label logit or blank logit means "no such arc"; a NaN or +inf
+    logit in an utterance's band (the blank logit included) gives that utterance a NaN cost and leaves the others
+    bit-identical. Returns float32 costs [B] on acts.device. The read-outs take blank_factorized=True
+    (monotonic_rnnt_align / _posteriors / _sample); the fused joint, monotonic_rnnt_path_loss and
+    monotonic_rnnt_expected_cost are softmax-only for now."""
+    result = MonotonicRNNTHatFunction.apply(acts, labels, input_lengths, label_lengths, alignment,
+                                            max_distance_from_alignment, blank_label)
+    assert result is not None
+    return result
+
+
 def _readout_length(prep, max_input_length, who):
     """Row length of a per-frame read-out: max_input_length, else the padded acts' frames, else the longest host length,
     else the alignment's row length."""
@@ -455,7 +509,7 @@ def _readout_length(prep, max_input_length, who):
 def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                          label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
                          max_distance_from_alignment: int = 0, blank_label: int = 0,
-                         max_input_length: Optional[int] = None):
+                         max_input_length: Optional[int] = None, blank_factorized: bool = False):
     """Best-path (Viterbi) alignment of every utterance: the single most probable monotonic path through the lattice
     the loss sums over (mrnnt_align / mrnnt_cpu_align, include/mrnnt.h). Arguments as monotonic_rnnt_loss; an
     `alignment` with `max_distance_from_alignment` restricts the search to the same band as the loss.
@@ -469,7 +523,8 @@ def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths
     On a tie the frame emits blank (the label arc is taken only when strictly more probable). An utterance without a
     finite path (masked -inf logits, a band no path fits) has cost +inf and its row -1; a NaN / +inf logit in its band
     gives cost NaN and the row -1. Not differentiable: requires_grad is ignored and plain tensors are returned.
-    GPU-resident lengths that fail validation surface through check_lengths() exactly as for the loss."""
+    GPU-resident lengths that fail validation surface through check_lengths() exactly as for the loss.
+    blank_factorized=True: the best path under monotonic_rnnt_hat_loss's distribution (mrnnt_hat_align)."""
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
     L = _readout_length(prep, max_input_length, "monotonic_rnnt_align")
@@ -477,7 +532,8 @@ def monotonic_rnnt_align(acts: torch.Tensor, labels: torch.Tensor, input_lengths
     B = prep.problem.B
     out = torch.empty((B, L), dtype=torch.int32, device=prep.device)
     costs = torch.empty(B, dtype=torch.float32, device=prep.device)
-    _call(prep, "align", _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs), pending=True)
+    _call(prep, "hat_align" if blank_factorized else "align", _ptr(ws), ws.numel(), _ptr(out), L, _ptr(costs),
+          pending=True)
     return out, costs
 
 
@@ -487,7 +543,7 @@ Posteriors = collections.namedtuple("Posteriors", ["blank", "label", "emit", "la
 def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                               label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
                               max_distance_from_alignment: int = 0, blank_label: int = 0,
-                              max_input_length: Optional[int] = None) -> Posteriors:
+                              max_input_length: Optional[int] = None, blank_factorized: bool = False) -> Posteriors:
     """Arc posteriors of the lattice the loss sums over -- the soft alignment (mrnnt_posteriors /
     mrnnt_cpu_posteriors, include/mrnnt.h): the forward pass with beta, then a read-out of its workspace on the same
     stream. Arguments as monotonic_rnnt_loss; with `alignment` and `max_distance_from_alignment` the posteriors are
@@ -506,11 +562,13 @@ def monotonic_rnnt_posteriors(acts: torch.Tensor, labels: torch.Tensor, input_le
     Rows no path can reach (outside the band, masked logits) are exactly 0. An utterance without a finite cost (no
     path: +inf; a NaN / +inf logit in its band) has NaN in all of its values; the other utterances are unaffected.
     Not differentiable: requires_grad is ignored and plain tensors are returned. GPU-resident lengths that fail
-    validation make every value NaN and surface through check_lengths() exactly as for the loss."""
+    validation make every value NaN and surface through check_lengths() exactly as for the loss.
+    blank_factorized=True: the posteriors (and costs) under monotonic_rnnt_hat_loss's distribution -- the same read-out
+    over the state of the factorised forward."""
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
     L = _readout_length(prep, max_input_length, "monotonic_rnnt_posteriors")
-    costs, ws = _forward(prep, with_beta=True)
+    costs, ws = _forward(prep, with_beta=True, hat=blank_factorized)
     B, dev = prep.problem.B, prep.device
     Sw = labels.size(1) if labels.dim() == 2 else prep.labels.size(1)
     blank = torch.empty(prep.acts.shape[:-1], dtype=torch.float32, device=dev)
@@ -535,7 +593,8 @@ def _sample_args(num_samples, seed, first_sample, where):
 def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                           label_lengths: torch.Tensor, num_samples: int, seed: int, first_sample: int = 0,
                           alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
-                          blank_label: int = 0, max_input_length: Optional[int] = None) -> Samples:
+                          blank_label: int = 0, max_input_length: Optional[int] = None,
+                          blank_factorized: bool = False) -> Samples:
     """Whole alignments drawn from the path posterior p(path | labels, acts) of the lattice the loss sums over
     (mrnnt_sample / mrnnt_cpu_sample, include/mrnnt.h): the forward pass with beta, then a read-out of its workspace
     on the same stream. Arguments as monotonic_rnnt_loss; with `alignment` and `max_distance_from_alignment` the
@@ -554,14 +613,16 @@ def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_length
     64, and first_sample = 8 continues where 8 samples stopped. An utterance without a finite cost has all its rows
     -1 and path costs +inf (no path) or NaN; the others are unaffected. Not differentiable: requires_grad is ignored
     and plain tensors are returned. GPU-resident lengths that fail validation give -1 / NaN everywhere and surface
-    through check_lengths() exactly as for the loss."""
+    through check_lengths() exactly as for the loss.
+    blank_factorized=True: draws, path costs and costs under monotonic_rnnt_hat_loss's distribution -- the same read-out
+    over the state of the factorised forward."""
     K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_sample")
     acts = acts.detach()
     prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
     L = _readout_length(prep, max_input_length, "monotonic_rnnt_sample")
     if K < 1:
         raise RuntimeError(f"monotonic_rnnt_sample: num_samples must be >= 1, got {K}")
-    costs, ws = _forward(prep, with_beta=True)
+    costs, ws = _forward(prep, with_beta=True, hat=blank_factorized)
     B, dev = prep.problem.B, prep.device
     out = torch.empty((B, K, L), dtype=torch.int32, device=dev)
     path_costs = torch.empty((B, K), dtype=torch.float32, device=dev)
@@ -762,6 +823,23 @@ class MonotonicRNNTLoss(torch.nn.Module):
         return loss
 
 
+class MonotonicRNNTHatLoss(torch.nn.Module):
+    """monotonic_rnnt_hat_loss as a module, in the shape of MonotonicRNNTLoss."""
+
+    def __init__(self, blank_label: int = 0) -> None:
+        super().__init__()
+        self.blank_label = blank_label
+        self.loss = MonotonicRNNTHatFunction.apply
+
+    def forward(self, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
+                label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
+                max_distance_from_alignment: int = 0) -> torch.Tensor:
+        loss = self.loss(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
+                         self.blank_label)
+        assert loss is not None
+        return loss
+
+
 class _Ext:
     """The reference's pybind extension functions (monotonic_rnnt.cu:155-164), same argument order.
 
@@ -817,4 +895,5 @@ monotonic_rnnt_cpp = _Ext()
 __all__ = ["MonotonicRNNTFunction", "monotonic_rnnt_loss", "MonotonicRNNTLoss", "monotonic_rnnt_cpp", "check_lengths",
            "monotonic_rnnt_align", "monotonic_rnnt_posteriors", "monotonic_rnnt_sample",
            "MonotonicRNNTPathFunction", "monotonic_rnnt_path_loss", "MonotonicRNNTExpectedCostFunction",
-           "monotonic_rnnt_expected_cost"]
+           "monotonic_rnnt_expected_cost", "MonotonicRNNTHatFunction", "monotonic_rnnt_hat_loss",
+           "MonotonicRNNTHatLoss"]
