@@ -507,7 +507,8 @@ typedef struct mrnnt_joint_problem {
 RNNTStatus mrnnt_joint_workspace_size(const mrnnt_joint_problem *p, size_t *bytes);
 
 /* (version 12) A host-known upper bound on the live-row count of mrnnt_joint_live_rows: the lattice rows inside the
- * monotonic band, from the host lengths (no device read). Size G / Hact with it under p->live_count_dev. */
+ * monotonic band, from the host lengths (no device read). Size G / Hact with it under p->live_count_dev. Unchanged for
+ * the factorised-blank calls (mrnnt_joint_hat_*). */
 RNNTStatus mrnnt_joint_row_bound(const mrnnt_joint_problem *p, int64_t *rows);
 
 /* Forward: costs_dev[b] = -log P(labels_b | enc_b, pred_b); with_beta as in mrnnt_forward. */
@@ -543,7 +544,8 @@ RNNTStatus mrnnt_joint_align(const mrnnt_joint_problem *p, void *workspace, size
  * grid_T >= max T_b and grid_S1 >= max S_b + 1 (when either per-row output is given), emit_stride >= max T_b and
  * time_stride >= max S_b are checked on the host, with the NULL workspace, before any device call
  * (RNNT_STATUS_INVALID_VALUE). Reads the workspace only; its launch counts under [2] of mrnnt_profile_read.
- * Asynchronous on `stream`, no host read. */
+ * Asynchronous on `stream`, no host read. Works unchanged after mrnnt_joint_hat_forward(with_beta = 1): the posteriors
+ * are then those of the factorised-blank distribution. */
 RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *p, const void *workspace, float *blank_post_dev,
                                   float *label_post_dev, int64_t grid_T, int64_t grid_S1, float *emit_dev,
                                   int64_t emit_stride, float *label_time_dev, int64_t time_stride, hipStream_t stream);
@@ -551,13 +553,16 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *p, const void *work
 /* mrnnt_sample for the fused joint, after mrnnt_joint_forward(with_beta = 1) on the same workspace and inputs: the
  * same walk, random numbers, outputs ([B, num_samples, out_stride] / [B, num_samples]), sentinels and host checks
  * (the joint's lengths are on the host: out_stride >= max T_b is checked here). The same launch on the joint's packed
- * lattice; reads the workspace, labels and the lengths only. Counts under [2] of mrnnt_profile_read. */
+ * lattice; reads the workspace, labels and the lengths only. Counts under [2] of mrnnt_profile_read. Works unchanged
+ * after mrnnt_joint_hat_forward(with_beta = 1): the paths are then drawn from the factorised-blank posterior. */
 RNNTStatus mrnnt_joint_sample(const mrnnt_joint_problem *p, const void *workspace, int num_samples, uint64_t seed,
                               int64_t first_sample, int *alignments_dev, int64_t out_stride, float *path_costs_dev,
                               hipStream_t stream);
 
 /* After mrnnt_joint_forward(with_beta=1): list the live lattice rows (those with a non-zero fp32 logit
- * gradient) in the workspace and write their number to *count_dev (device uint64). */
+ * gradient) in the workspace and write their number to *count_dev (device uint64). Works unchanged after
+ * mrnnt_joint_hat_forward(with_beta = 1): the threshold is on the row's occupancy cb + ce, which bounds every
+ * factorised gradient element, so a row left out is all zero there too (a kept row may still be: time, not results). */
 RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *p, void *workspace, unsigned long long *count_dev,
                                  hipStream_t stream);
 
@@ -575,7 +580,8 @@ RNNTStatus mrnnt_joint_backward(const mrnnt_joint_problem *p, void *workspace, i
  * tiles (mrnnt_joint_gemm.hip): the dH GEMM with the tanh derivative in its epilogue. weight_t is the weight
  * transposed, bf16 [H, V] row-major; Hact as mrnnt_joint_backward wrote it (row stride p->hact_ld, 0 = H). Needs
  * H = 256 or 512 and V a multiple of 8 (RNNT_STATUS_INVALID_VALUE otherwise: use a library GEMM for dH and
- * mrnnt_joint_reduce with Hact). Sum dpre with mrnnt_joint_reduce_pre. */
+ * mrnnt_joint_reduce with Hact). Sum dpre with mrnnt_joint_reduce_pre. Works unchanged after
+ * mrnnt_joint_hat_backward. */
 RNNTStatus mrnnt_joint_dpre(const mrnnt_joint_problem *p, int64_t n_live, const void *G, const void *weight_t,
                             const void *Hact, void *dpre, hipStream_t stream);
 
@@ -583,7 +589,8 @@ RNNTStatus mrnnt_joint_dpre(const mrnnt_joint_problem *p, int64_t n_live, const 
  * dpre = dH * (1 - Hact^2) into d_enc (fp32, enc's [B, enc_stride/H, H] shape; rows (b, t < T_b) are
  * overwritten) and d_pred (fp32, pred's shape; added to: zero it first). Zero d_enc's padding rows yourself.
  * Hact is required (RNNT_STATUS_INVALID_VALUE when NULL with n_live > 0). Every sum has a fixed order (bitwise reproducible). p->reduce_scratch (version 9) lets it run on blocks of frames
- * whose d_pred sums are then added in block order; see mrnnt_joint_reduce_scratch_bytes. */
+ * whose d_pred sums are then added in block order; see mrnnt_joint_reduce_scratch_bytes. Works unchanged after
+ * mrnnt_joint_hat_backward (as does mrnnt_joint_reduce_pre). */
 RNNTStatus mrnnt_joint_reduce(const mrnnt_joint_problem *p, void *workspace, int64_t n_live, const void *dH,
                               const void *Hact, float *d_enc, float *d_pred, hipStream_t stream);
 
@@ -692,6 +699,38 @@ RNNTStatus mrnnt_joint_expect_rows(const mrnnt_joint_problem *p, void *workspace
                                    unsigned long long *count_dev, hipStream_t stream);
 RNNTStatus mrnnt_joint_expect_backward(const mrnnt_joint_problem *p, void *workspace, int64_t n_rows, void *G,
                                        void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream);
+
+/* mrnnt_hat_forward / mrnnt_hat_backward / mrnnt_hat_align for the fused joint (an addition to version 13:
+ * MRNNT_VERSION and both structs are unchanged, so callers that may meet an older build of version 13 probe for the
+ * symbol mrnnt_joint_hat_forward): the factorised-blank (HAT) loss of the logits the joint never stores. Blank is a
+ * Bernoulli on its own logit z_b and the labels a softmax over the other V - 1 logits,
+ *   lpb = log sigmoid(z_b),   lpe = log sigmoid(-z_b) + z_l - LSE_{v != b} z_v,
+ * with the rules of mrnnt_hat_forward: the blank logit is masked out of the row's max and sum (never subtracted
+ * afterwards); z_b = +inf or a NaN / +inf logit anywhere in the row makes both NaN; a label equal to blank is no arc; a
+ * row whose non-blank logits are all -inf has no label arc and an untouched blank arc. The logit gradient is
+ *   g[b] = ce sigmoid(z_b) - cb sigmoid(-z_b),   g[v != b] = ce (exp(z_v - LSE_{u != b} z_u) - [v == label(s)])
+ * times grad_scale, cb / ce the blank / label arc posteriors of the row.
+ *   mrnnt_joint_hat_forward: mrnnt_joint_forward with the factorised-blank joint pass; same workspace
+ *       (mrnnt_joint_workspace_size), arguments, host checks and alignment restriction.
+ *   mrnnt_joint_hat_align: mrnnt_joint_align under the factorised probabilities; same contract and host checks.
+ *   mrnnt_joint_hat_backward: mrnnt_joint_backward with the factorised-blank row coefficients, after
+ *       mrnnt_joint_hat_forward(with_beta = 1) and mrnnt_joint_live_rows on the same workspace. G, Hact, bt_idx, bs_idx,
+ *       grad_scale, p->hact_ld, p->dbias and p->live_count_dev (n_live then a host bound, rows [count, n_live) zeroed)
+ *       as there. Every factorised gradient element is at most cb + ce in magnitude, the occupancy the live-row list
+ *       thresholds, so a row it leaves out is all zero in fp32. An utterance without a path (ll = -inf, cost +inf)
+ *       gets exact zeros in its rows of G -- not the NaN of mrnnt_joint_backward / mrnnt_hat_backward -- so that it
+ *       does not turn dweight and dbias, which sum over the batch, into NaN; a NaN cost keeps NaN gradients.
+ * mrnnt_joint_posteriors, mrnnt_joint_sample, mrnnt_joint_live_rows, mrnnt_joint_reduce, mrnnt_joint_reduce_pre,
+ * mrnnt_joint_dpre and mrnnt_joint_row_bound work unchanged after mrnnt_joint_hat_forward(with_beta = 1): they read the
+ * recursion's state and the row lists, never the logits or the meaning of the denominator. Costs and all four
+ * gradients are bitwise reproducible. The launches count under mrnnt_profile_read as those of mrnnt_joint_*. */
+RNNTStatus mrnnt_joint_hat_forward(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                   float *costs_dev, int with_beta, hipStream_t stream);
+RNNTStatus mrnnt_joint_hat_backward(const mrnnt_joint_problem *p, void *workspace, int64_t n_live,
+                                    const float *grad_scale, void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx,
+                                    hipStream_t stream);
+RNNTStatus mrnnt_joint_hat_align(const mrnnt_joint_problem *p, void *workspace, size_t workspace_bytes,
+                                 int *alignment_out_dev, int64_t out_stride, float *costs_dev, hipStream_t stream);
 
 /* Nontemporal zero fill of `bytes` (a multiple of 16) at `dst` (16-byte aligned device memory), in the gradient
  * pass's store pattern. The Python surface times it once over a newly allocated large grads buffer to pick a

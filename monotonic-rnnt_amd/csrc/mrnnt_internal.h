@@ -81,7 +81,7 @@ struct DevProblem {
     const float *ex_wb = nullptr, *ex_we = nullptr;
     const float *ex_ge = nullptr, *ex_gc = nullptr;
     // mrnnt_hat_* (factorised blank): the log-softmax launch takes the kernels whose rows keep the blank logit out of
-    // the denominator (launch_softmax dispatches on it on the host; no kernel reads it)
+    // the denominator (launch_softmax and launch_joint_forward dispatch on it on the host; no kernel reads it)
     int hat = 0;
 };
 
@@ -132,9 +132,12 @@ hipError_t launch_row_list(const DevProblem &p, int mode, int64_t *col_cnt, int 
 hipError_t launch_joint_forward(const DevProblem &p, const JointArgs &j, hipStream_t stream);
 // flag = 1 when max_v (sum_h |W[v, h]| + |bias[v]|) <= 64 (then |z| <= 64 for every logit: |tanh| <= 1), else 0
 hipError_t launch_joint_wbound(const unsigned short *W, const float *bias, int V, int H, int *flag, hipStream_t stream);
-// path_coef: the rows' coefficients are the path weights Wb / We (p.alpha / p.beta after launch_path_coef) and den,
-// g = (Wb + We) softmax - [blank] Wb - [label] We; j.scale is not read
-hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream, bool path_coef = false);
+// coef: the rows' coefficients. kJointCoefLoss: the loss's (alpha / beta / ll, times j.scale). kJointCoefPath: the path
+// weights Wb / We (p.alpha / p.beta after launch_path_coef) and den, g = (Wb + We) softmax - [blank] Wb - [label] We;
+// j.scale is not read. kJointCoefHat: the factorised-blank loss's (hat_coef, mrnnt_hat.h), after a forward with p.hat
+constexpr int kJointCoefLoss = 0, kJointCoefPath = 1, kJointCoefHat = 2;
+hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream,
+                                 int coef = kJointCoefLoss);
 hipError_t launch_joint_reduce(const DevProblem &p, const JointArgs &j, const int64_t *off, int T_max, int S_max,
                                const unsigned short *dH, float *d_enc, float *d_pred, void *scratch,
                                size_t scratch_bytes, hipStream_t stream);

@@ -23,6 +23,8 @@
 #include <utility>
 
 #include "mrnnt_device.h"
+#include "mrnnt_hat.h"  // HatCoef / hat_coef (the factorised-blank row coefficients)
+#include "mrnnt_lsm.h"  // hat_lp (the factorised-blank log-probs of a row)
 
 namespace mrnnt {
 
@@ -444,6 +446,16 @@ __device__ __forceinline__ float max3(float a, float b, float c) {
     return r;
 }
 
+// The factorised blank (HAT): register r of this lane's 16 becomes -inf (r = -1: none). Sixteen selects on the
+// registers themselves (compile-time indices; an indexed array would go through scratch), run in the blank's chunk only.
+__device__ __forceinline__ void drop_reg(f2 (&x)[8], int r) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        x[k].x = (2 * k == r) ? NEG_INF_F : x[k].x;
+        x[k].y = (2 * k + 1 == r) ? NEG_INF_F : x[k].y;
+    }
+}
+
 // Chunk loop: a workgroup of NW waves (NW = 8: two waves per SIMD, 256 rows) shares each W chunk; NB LDS buffers
 // keep NB - 1 chunk DMAs in flight; one raw s_barrier per chunk. `S` = vector stores the epilogue issues per chunk
 // on every wave (0 forward, 4 backward; -1 = unknown): the wait before chunk c leaves the later DMAs and the
@@ -506,7 +518,13 @@ __device__ __forceinline__ float *load_bias(const JointArgs &j, int V, unsigned 
 // two waves per SIMD: the compiler keeps each kernel within 256 registers per lane
 // TR: the development build's timeline stamps (JOINT_MARK), instantiated only when the joint_trace knob asks for them:
 // the stamps (a scalar clock read and a store per mark, one inside the chunk loop) cost that build's forward ~15 %
-template <int KS, int NB, int NW, int RG, bool TR = false>
+// HAT: the factorised-blank flavour (mrnnt_joint_hat_*, chosen on the host from DevProblem::hat): den' = -LSE over the
+// non-blank logits and hat_lp's pair (mrnnt_lsm.h, the helper of the acts kernels). The blank logit never enters the
+// max or the sum: its chunk is wave-uniform, the lane and register that hold it are acc_reg_of's, and in that chunk
+// that register's term is -inf before the max and before the exp (drop_reg) -- in all three epilogue forms. Subtracting
+// exp(z_b) from a sum over the whole row instead cancels to nothing once z_b dominates (z_b = +55 in the plain form,
+// inside the +-64 bound). The plain sum stays safe with one term fewer, so joint_wbound_kernel decides as before.
+template <int KS, int NB, int NW, int RG, bool TR = false, bool HAT = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void joint_fwd_kernel(DevProblem p,
                                                                                              JointArgs j) {
     extern __shared__ __attribute__((aligned(16))) unsigned short wsh[];
@@ -547,6 +565,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             }
         }
     };
+    // HAT: this lane's register of the blank logit in chunk c, -1 where another chunk or the other lane half holds it
+    auto blank_reg = [&](int c) {
+        const int jb = blank - 32 * c;
+        return (jb >= 0 && jb < 32) ? acc_reg_of(jb, half) : -1;
+    };
+    // HAT: the row's outputs from den' (a label equal to blank is no arc; an out-of-range label NaN, as without HAT)
+    auto write_hat = [&](double den) {
+        const float zl = q.lab == blank ? NEG_INF_F : (q.lab >= 0 ? ze : (q.lab == -2 ? __builtin_nanf("") : 0.0f));
+        p.den[q.row] = (float)den;
+        p.lp[q.row] = hat_lp(zb, zl, den);
+    };
     // Bounded weights (j.wplain: |z| <= 64 for every logit, joint_wbound_kernel): a plain exp-sum -- 1024 terms of
     // at most e^64 cannot overflow fp32 and the largest cannot underflow -- without the running max, whose
     // per-chunk max / rescale chain cost 15 % of the forward. Otherwise the online log-sum-exp.
@@ -559,15 +588,30 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         chunk_loop<KS, NB, NW, RG, TR>(j, V, wsh, bfr, lane, 0, [&](const f32x16 &acc, int c) {
             f2 s2 = {0.0f, 0.0f};
             f2 a2[8];
+            if constexpr (HAT) {
+                f2 t[8];
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const f4 bv = *reinterpret_cast<const f4 *>(bias2 + 32 * c + 8 * q4 + 4 * half);
-                a2[2 * q4] = (f2){acc[4 * q4], acc[4 * q4 + 1]};
-                a2[2 * q4 + 1] = (f2){acc[4 * q4 + 2], acc[4 * q4 + 3]};
-                const f2 t0 = fma2(a2[2 * q4], l2e, (f2){bv.x, bv.y});
-                const f2 t1 = fma2(a2[2 * q4 + 1], l2e, (f2){bv.z, bv.w});
-                s2 = add2(s2, (f2){fast_exp2(t0.x), fast_exp2(t0.y)});
-                s2 = add2(s2, (f2){fast_exp2(t1.x), fast_exp2(t1.y)});
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const f4 bv = *reinterpret_cast<const f4 *>(bias2 + 32 * c + 8 * q4 + 4 * half);
+                    a2[2 * q4] = (f2){acc[4 * q4], acc[4 * q4 + 1]};
+                    a2[2 * q4 + 1] = (f2){acc[4 * q4 + 2], acc[4 * q4 + 3]};
+                    t[2 * q4] = fma2(a2[2 * q4], l2e, (f2){bv.x, bv.y});
+                    t[2 * q4 + 1] = fma2(a2[2 * q4 + 1], l2e, (f2){bv.z, bv.w});
+                }
+                if (blank >= 32 * c && blank < 32 * c + 32) drop_reg(t, blank_reg(c));  // the blank's chunk only
+#pragma unroll
+                for (int k = 0; k < 8; ++k) s2 = add2(s2, (f2){fast_exp2(t[k].x), fast_exp2(t[k].y)});
+            } else {
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const f4 bv = *reinterpret_cast<const f4 *>(bias2 + 32 * c + 8 * q4 + 4 * half);
+                    a2[2 * q4] = (f2){acc[4 * q4], acc[4 * q4 + 1]};
+                    a2[2 * q4 + 1] = (f2){acc[4 * q4 + 2], acc[4 * q4 + 3]};
+                    const f2 t0 = fma2(a2[2 * q4], l2e, (f2){bv.x, bv.y});
+                    const f2 t1 = fma2(a2[2 * q4 + 1], l2e, (f2){bv.z, bv.w});
+                    s2 = add2(s2, (f2){fast_exp2(t0.x), fast_exp2(t0.y)});
+                    s2 = add2(s2, (f2){fast_exp2(t1.x), fast_exp2(t1.y)});
+                }
             }
             sum += s2.x + s2.y;
             const int jb = blank - 32 * c;
@@ -594,6 +638,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         chunk_loop<KS, NB, NW, RG, TR>(j, V, wsh, bfr, lane, 0, [&](const f32x16 &acc, int c) {
             f2 z[8];
             logits2(acc, bias, c, half, z);
+            if constexpr (HAT) {  // z_b picked first, then out of the row (the blank's chunk only)
+                capture(z, c);
+                if (blank >= 32 * c && blank < 32 * c + 32) drop_reg(z, blank_reg(c));
+            }
             f2 s2 = {0.0f, 0.0f};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -601,7 +649,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 s2 = add2(s2, (f2){fast_exp2(t.x), fast_exp2(t.y)});
             }
             sum += s2.x + s2.y;
-            capture(z, c);
+            if constexpr (!HAT) capture(z, c);
             if (c == 0) FWD_MARK(3);
         });
     }
@@ -613,8 +661,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         if (!fe && fe2) ze = ze2;
         if (q.valid && half == 0) {
             const double den = -log_row_sum(sum);
-            p.den[q.row] = (float)den;
-            p.lp[q.row] = Lp{(double)zb + den, (q.lab >= 0 ? (double)ze : (q.lab == -2 ? __builtin_nan("") : 0.0)) + den};
+            if constexpr (HAT) {
+                write_hat(den);
+            } else {
+                p.den[q.row] = (float)den;
+                p.lp[q.row] =
+                    Lp{(double)zb + den, (q.lab >= 0 ? (double)ze : (q.lab == -2 ? __builtin_nan("") : 0.0)) + den};
+            }
         }
         FWD_MARK(4);
         return;
@@ -622,6 +675,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     chunk_loop<KS, NB, NW, RG, TR>(j, V, wsh, bfr, lane, 0, [&](const f32x16 &acc, int c) {
         f2 z[8];
         logits2(acc, bias, c, half, z);
+        if constexpr (HAT) {  // z_b picked first, then out of the row before this chunk's max
+            capture(z, c);
+            if (blank >= 32 * c && blank < 32 * c + 32) drop_reg(z, blank_reg(c));
+        }
         float cm = fmaxf(z[0].x, z[0].y);
 #pragma unroll
         for (int k = 1; k < 8; ++k) cm = max3(cm, z[k].x, z[k].y);
@@ -636,7 +693,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
         sum = sum * fast_exp2((m - mr) * kLog2e) + (s2.x + s2.y);
         m = mn;
-        capture(z, c);
+        if constexpr (!HAT) capture(z, c);
         if (c == 0) FWD_MARK(3);
     });
     // merge the two lane halves (same row, disjoint vocabulary)
@@ -650,8 +707,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     if (!fe && fe2) ze = ze2;
     if (q.valid && half == 0) {
         const double den = -(double)mn - log_row_sum(sum);
-        p.den[q.row] = (float)den;
-        p.lp[q.row] = Lp{(double)zb + den, (q.lab >= 0 ? (double)ze : (q.lab == -2 ? __builtin_nan("") : 0.0)) + den};
+        if constexpr (HAT) {
+            write_hat(den);
+        } else {
+            p.den[q.row] = (float)den;
+            p.lp[q.row] = Lp{(double)zb + den, (q.lab >= 0 ? (double)ze : (q.lab == -2 ? __builtin_nan("") : 0.0)) + den};
+        }
     }
     FWD_MARK(4);
 }
@@ -690,8 +751,11 @@ struct LossCoef {
     __device__ __forceinline__ float out(float e) const { return e * sc; }
     __device__ __forceinline__ float out_blank(float e) const { return (e - cb) * sc; }
     __device__ __forceinline__ float out_label(float e) const { return (e - ce) * sc; }
-    __device__ __forceinline__ float sum_blank() const { return cb * sc; }
+    // what the dbias column sum, which holds out(e) for every entry, loses at the row's blank / label entry (e: the
+    // blank entry's value, for a policy whose blank element does not follow from it)
+    __device__ __forceinline__ float sum_blank(float) const { return cb * sc; }
     __device__ __forceinline__ float sum_label() const { return ce * sc; }
+    static constexpr bool kHat = false;
 };
 
 // Path scores (mrnnt_joint_path_backward): g = wocc * softmax - [blank] Wb - [label] We, the formula of PathRows::grad
@@ -718,8 +782,45 @@ struct PathCoef {
     __device__ __forceinline__ float out(float e) const { return wocc * e; }
     __device__ __forceinline__ float out_blank(float e) const { return wocc * e - cb; }
     __device__ __forceinline__ float out_label(float e) const { return wocc * e - ce; }
-    __device__ __forceinline__ float sum_blank() const { return cb; }
+    __device__ __forceinline__ float sum_blank(float) const { return cb; }
     __device__ __forceinline__ float sum_label() const { return ce; }
+    static constexpr bool kHat = false;
+};
+
+// The factorised blank (mrnnt_joint_hat_backward): the coefficients of hat_coef (mrnnt_hat.h, the definition HatRows
+// streams stored logits with), g[v != b] = sc (exp2(z log2 e + c2) - [v == label] ce) with ce folded into c2, and the
+// blank element sc gb -- gb = ce sigmoid(z_b) - cb sigmoid(-z_b), formed once per row from lpb -- whatever e is.
+// kHat: the kernels take the blank logit out of the row before the exp (-inf in its register, in its chunk only), so
+// the blank entry's e is exactly 0 -- not exp(z_b + den' + log ce), which overflows fp32 once the blank dominates the
+// row -- and the dbias column sum, which holds out(0) = 0 there, is corrected to sc gb by sum_blank.
+struct HatJointCoef {
+    float c2, ce, gb, sc;
+    int lab;
+    __device__ __forceinline__ void clear() {
+        c2 = ce = gb = sc = 0.0f;
+        lab = -1;
+    }
+    __device__ __forceinline__ void stage(const DevProblem &p, const JointArgs &j, const RowPos &q) {
+        HatCoef rc;
+        const double ll = p.ll[q.b];
+        hat_coef(p, q.t, q.T, q.S, q.s, q.row, ll, p.labels + (int64_t)q.b * p.label_stride, rc);
+        c2 = rc.c2, ce = rc.ce, gb = rc.gb, lab = rc.lab;
+        // An utterance without a path (ll = -inf, cost +inf: e.g. every label masked by a -inf bias) has no arc
+        // posteriors, and exp(... - ll) is NaN in every coefficient. Its rows come out exact zeros here: d_weight and
+        // d_bias sum over the batch, and one such utterance must not turn the other utterances' share of them into
+        // NaN. (A NaN ll -- a NaN / +inf logit -- keeps its NaN gradients.)
+        if (ll == NEG_INF_D) {
+            c2 = NEG_INF_F;
+            ce = gb = 0.0f;
+        }
+        sc = j.scale ? j.scale[q.b] : 1.0f;
+    }
+    __device__ __forceinline__ float out(float e) const { return e * sc; }
+    __device__ __forceinline__ float out_blank(float) const { return gb * sc; }
+    __device__ __forceinline__ float out_label(float e) const { return (e - ce) * sc; }
+    __device__ __forceinline__ float sum_blank(float e) const { return out(e) - gb * sc; }
+    __device__ __forceinline__ float sum_label() const { return ce * sc; }
+    static constexpr bool kHat = true;
 };
 
 template <int KS, int NB, int NW, int RG, class RC>
@@ -751,14 +852,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     chunk_loop<KS, NB, NW, RG>(j, V, wsh, bfr, lane, leave ? 4 : -1, [&](const f32x16 &acc, int c) {
         f2 g[8];
         logits2(acc, bias, c, half, g);
+        const int jb = blank - 32 * c;
+        const int rb = (jb >= 0 && jb < 32) ? acc_reg_of(jb, half) : -1;
+        if constexpr (RC::kHat)  // the blank logit out of the row before the exp: its entry's e is 0
+            if (jb >= 0 && jb < 32) drop_reg(g, rb);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const f2 t = fma2(g[k], l2e, c2);
             g[k] = (f2){fast_exp2(t.x), fast_exp2(t.y)};
         }
         // the <= 2 corrected entries of the row are rewritten by a second (2-byte) store after the vector store
-        const int jb = blank - 32 * c;
-        const int rb = (jb >= 0 && jb < 32) ? acc_reg_of(jb, half) : -1;
         const int jl = rc.lab - 32 * c;
         const int rl = acc_reg_of(jl & 31, half);
         const bool mine = rc.lab >= 0 && jl >= 0 && jl < 32 && rl >= 0;
@@ -870,6 +973,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             for (int rt = 0; rt < 2; ++rt) {
                 float x[8];
                 logits8<KS>(acc, bv, rt, x);
+                if constexpr (RC::kHat) {  // the blank logit out of the row before the exp (its chunk only): e = 0 there
+                    if (jb >= 0 && jb < 32) {
+                        const int kb = hb ? pick8_index(jb) : -1;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) x[k] = (k == kb) ? NEG_INF_F : x[k];
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < 8; ++k) x[k] = fast_exp2(fmaf(x[k], kLog2e, rc[rt].c2));
                 // the <= 2 corrected entries of the row are rewritten by a second (2-byte) store after the vector store
@@ -899,7 +1009,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     if (mine) grow[rt][rc[rt].lab] = IoBF16::from_f(rc[rt].out_label(gl));
                     if (j.dbias) {  // the two corrected entries: the column sums above hold them uncorrected
                         const int kb = hb ? pick8_index(jb) : -1, kl = mine ? pick8_index(jl & 31) : -1;
-                        const float db = rc[rt].sum_blank(), dl = rc[rt].sum_label();
+                        const float db = rc[rt].sum_blank(gb), dl = rc[rt].sum_label();
 #pragma unroll
                         for (int k = 0; k < 8; ++k) {
                             if (k == kb) cs[k] -= db;
@@ -1340,7 +1450,8 @@ hipError_t launch_joint_reduce(const DevProblem &p, const JointArgs &j_in, const
 }
 
 // kernel of a launch shape: MF = the backward's MFMA tile (32: 32x32x16, 16: 16x16x32); the forward runs 32x32x16;
-// RC = the backward's row coefficients (LossCoef / PathCoef)
+// RC = the backward's row coefficients (LossCoef / PathCoef / HatJointCoef); the forward takes its flavour from
+// RC::kHat (HatJointCoef: the factorised-blank epilogue)
 template <int KS, int NB, int NW, int MF, bool BWD, int RG, class RC>
 static hipError_t launch_knw(const DevProblem &p, const JointArgs &j, size_t lds, hipStream_t stream) {
     const int64_t blocks = (j.n + 32 * NW - 1) / (32 * NW);
@@ -1348,6 +1459,7 @@ static hipError_t launch_knw(const DevProblem &p, const JointArgs &j, size_t lds
     void (*kern)(DevProblem, JointArgs);
     if constexpr (MF == 16 && BWD) kern = joint_bwd16_kernel<KS, NB, NW, RC>;
     else if constexpr (BWD) kern = joint_bwd_kernel<KS, NB, NW, RG, RC>;
+    else if constexpr (RC::kHat) kern = joint_fwd_kernel<KS, NB, NW, RG, false, true>;
     else {
         kern = joint_fwd_kernel<KS, NB, NW, RG>;
         if constexpr (kVariants)
@@ -1392,9 +1504,12 @@ static hipError_t launch_kb(const DevProblem &p, const JointArgs &j, hipStream_t
     return launch_kt<KS, kDefault, BWD, RC>(p, j, stream);
 }
 
-// pass: 0 forward, 1 the loss's gradient pass, 2 the path scores' (PathCoef)
+// pass: 0 forward (p.hat: the factorised-blank flavour), 1 the loss's gradient pass, 2 the path scores' (PathCoef),
+// 3 the factorised-blank loss's (HatJointCoef)
 template <int KS>
 static hipError_t launch_kh(const DevProblem &p, const JointArgs &j, int pass, hipStream_t stream) {
+    if (pass == 3) return launch_kb<KS, true, HatJointCoef>(p, j, stream);
+    if (pass == 0 && p.hat) return launch_kb<KS, false, HatJointCoef>(p, j, stream);
     if (pass == 2) return launch_kb<KS, true, PathCoef>(p, j, stream);
     return pass ? launch_kb<KS, true, LossCoef>(p, j, stream) : launch_kb<KS, false, LossCoef>(p, j, stream);
 }
@@ -1482,8 +1597,8 @@ hipError_t launch_joint_forward(const DevProblem &p, const JointArgs &j, hipStre
     return launch_joint(p, j, 0, stream);
 }
 
-hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream, bool path_coef) {
-    return launch_joint(p, j, path_coef ? 2 : 1, stream);
+hipError_t launch_joint_backward(const DevProblem &p, const JointArgs &j, hipStream_t stream, int coef) {
+    return launch_joint(p, j, coef == kJointCoefHat ? 3 : coef == kJointCoefPath ? 2 : 1, stream);
 }
 
 }  // namespace mrnnt

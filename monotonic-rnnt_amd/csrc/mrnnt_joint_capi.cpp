@@ -5,7 +5,9 @@
 // given alignments (mrnnt_path.hip's walk / hull / score / coef launches around the joint pass over the hull rows) and
 // run the gradient pass over the path-live rows; mrnnt_joint_expect_* put the expectation recursion of
 // mrnnt_expect.hip behind the joint forward, form the expected cost's row weights (launch_expect_coef) and run the same
-// gradient pass over the expect-live rows. Asynchronous on the caller's stream, no host synchronisation.
+// gradient pass over the expect-live rows; mrnnt_joint_hat_forward / _backward / _align are the factorised-blank (HAT)
+// loss on the same plan, workspace and row lists -- thin wrappers over the *_impl functions below with a `hat` flag.
+// Asynchronous on the caller's stream, no host synchronisation.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -122,15 +124,17 @@ JointArgs joint_args(const mrnnt_joint_problem *jp, const JointPlan &jl, void *w
 
 // What mrnnt_joint_forward and mrnnt_joint_align share after the plan: pointer and workspace checks, the lattice (and
 // the alignment band), then the joint log-softmax pass that leaves lpb / lpe of every row the recursion can use in the
-// workspace. *out: the device problem for the launch that follows (launch_dp / launch_viterbi).
+// workspace. *out: the device problem for the launch that follows (launch_dp / launch_viterbi). hat: the
+// factorised-blank flavour of the joint pass (DevProblem::hat): den' and hat_lp's pair in the same arrays.
 RNNTStatus joint_log_softmax(const mrnnt_joint_problem *jp, const JointPlan &jl, void *ws, size_t ws_bytes,
-                             int64_t t_cap, hipStream_t stream, DevProblem *out) {
+                             int64_t t_cap, hipStream_t stream, DevProblem *out, bool hat = false) {
     RNNTStatus st = check_joint_pointers(jp);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, jl.total)) != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = jl.base;
     const mrnnt_problem p = base_problem(jp);  // host lengths, no caller lattice: the setup kernel builds the offsets
     DevProblem d = make_dev(&p, pl, ws);
+    d.hat = hat ? 1 : 0;
     LatticeOpts o;
     o.t_cap = t_cap;
     if ((st = prepare_lattice(&p, pl, d, ws, o, stream)) != RNNT_STATUS_SUCCESS) return st;
@@ -268,8 +272,9 @@ DevProblem joint_expect_dev(const mrnnt_problem *p, const JointExpectPlan &ep, v
 // mrnnt_joint_backward / mrnnt_joint_path_backward / mrnnt_joint_expect_backward: the MFMA gradient pass over the rows
 // of the last list built, with the loss's row coefficients (alpha / beta / ll, times scale), the path weights (path:
 // Wb / We in alpha / beta) or the expected cost's (expect: the path coefficients on a device problem whose alpha / beta
-// point at the coefficient launch's Wb / We arrays -- the same kernel instantiation).
-enum JointCoef { kCoefLoss, kCoefPath, kCoefExpect };
+// point at the coefficient launch's Wb / We arrays -- the same kernel instantiation) or the factorised-blank loss's
+// (hat: hat_coef over the state of mrnnt_joint_hat_forward).
+enum JointCoef { kCoefLoss, kCoefPath, kCoefExpect, kCoefHat };
 
 RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale, void *G,
                           void *Hact, int64_t *bt_idx, int64_t *bs_idx, JointCoef coef, hipStream_t stream) {
@@ -309,7 +314,8 @@ RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_liv
         return fail(RNNT_STATUS_INVALID_VALUE, "dbias needs a bias (the workspace holds its partial sums only then)");
     if (jp->dbias) j.dbias_part = carve<float>(ws, jl.off_dbias);
     hipError_t e = timed(K_JOINT_BWD, stream, [&] {
-        const hipError_t eb = launch_joint_backward(d, j, stream, coef != kCoefLoss);
+        const hipError_t eb = launch_joint_backward(
+            d, j, stream, coef == kCoefLoss ? kJointCoefLoss : coef == kCoefHat ? kJointCoefHat : kJointCoefPath);
         if (eb != hipSuccess || !jp->live_count_dev) return eb;
         return launch_joint_tail_zero(j.G, jp->V, j.Hact, j.hact_ld, n_live, jp->live_count_dev, stream);
     });
@@ -318,6 +324,40 @@ RNNTStatus joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_liv
         e = launch_joint_dbias_sum(j, jp->V, stream);
         if (e != hipSuccess) return fail_hip(e, "joint dbias sum kernels");
     }
+    return RNNT_STATUS_SUCCESS;
+}
+
+// mrnnt_joint_forward / mrnnt_joint_hat_forward
+RNNTStatus joint_forward_impl(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
+                              hipStream_t stream, bool hat) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d;
+    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, 0, stream, &d, hat)) != RNNT_STATUS_SUCCESS) return st;
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_dp(d, jl.base.S_max, with_beta ? 1 : 0, costs_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "alpha/beta kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+// mrnnt_joint_align / mrnnt_joint_hat_align
+RNNTStatus joint_align_impl(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, int *alignment_out_dev,
+                            int64_t out_stride, float *costs_dev, hipStream_t stream, bool hat) {
+    JointPlan jl;
+    RNNTStatus st = make_joint_plan(jp, &jl);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
+    if ((st = check_row_stride("alignment_out", out_stride, "input", jl.base.T_max, false, 0)) != RNNT_STATUS_SUCCESS)
+        return st;
+    DevProblem d;
+    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, out_stride, stream, &d, hat)) != RNNT_STATUS_SUCCESS) return st;
+    // jp->alignment may be alignment_out_dev itself: the band kernels have consumed it (stream order), the joint
+    // pass and the Viterbi launch read only the band arrays
+    const hipError_t e = timed(K_DP, stream, [&] {
+        return launch_viterbi(d, jl.base.S_max, alignment_out_dev, out_stride, costs_dev, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -345,34 +385,22 @@ RNNTStatus mrnnt_joint_row_bound(const mrnnt_joint_problem *jp, int64_t *rows) {
 
 RNNTStatus mrnnt_joint_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, float *costs_dev,
                                int with_beta, hipStream_t stream) {
-    JointPlan jl;
-    RNNTStatus st = make_joint_plan(jp, &jl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    DevProblem d;
-    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, 0, stream, &d)) != RNNT_STATUS_SUCCESS) return st;
-    const hipError_t e =
-        timed(K_DP, stream, [&] { return launch_dp(d, jl.base.S_max, with_beta ? 1 : 0, costs_dev, stream); });
-    if (e != hipSuccess) return fail_hip(e, "alpha/beta kernel");
-    return RNNT_STATUS_SUCCESS;
+    return joint_forward_impl(jp, ws, ws_bytes, costs_dev, with_beta, stream, false);
+}
+
+RNNTStatus mrnnt_joint_hat_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, float *costs_dev,
+                                   int with_beta, hipStream_t stream) {
+    return joint_forward_impl(jp, ws, ws_bytes, costs_dev, with_beta, stream, true);
 }
 
 RNNTStatus mrnnt_joint_align(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, int *alignment_out_dev,
                              int64_t out_stride, float *costs_dev, hipStream_t stream) {
-    JointPlan jl;
-    RNNTStatus st = make_joint_plan(jp, &jl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if (!alignment_out_dev) return fail(RNNT_STATUS_INVALID_VALUE, "alignment_out is null");
-    if ((st = check_row_stride("alignment_out", out_stride, "input", jl.base.T_max, false, 0)) != RNNT_STATUS_SUCCESS)
-        return st;
-    DevProblem d;
-    if ((st = joint_log_softmax(jp, jl, ws, ws_bytes, out_stride, stream, &d)) != RNNT_STATUS_SUCCESS) return st;
-    // jp->alignment may be alignment_out_dev itself: the band kernels have consumed it (stream order), the joint
-    // pass and the Viterbi launch read only the band arrays
-    const hipError_t e = timed(K_DP, stream, [&] {
-        return launch_viterbi(d, jl.base.S_max, alignment_out_dev, out_stride, costs_dev, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "viterbi kernel");
-    return RNNT_STATUS_SUCCESS;
+    return joint_align_impl(jp, ws, ws_bytes, alignment_out_dev, out_stride, costs_dev, stream, false);
+}
+
+RNNTStatus mrnnt_joint_hat_align(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes, int *alignment_out_dev,
+                                 int64_t out_stride, float *costs_dev, hipStream_t stream) {
+    return joint_align_impl(jp, ws, ws_bytes, alignment_out_dev, out_stride, costs_dev, stream, true);
 }
 
 RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws, float *blank_post_dev,
@@ -434,6 +462,11 @@ RNNTStatus mrnnt_joint_live_rows(const mrnnt_joint_problem *jp, void *ws, unsign
 RNNTStatus mrnnt_joint_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale,
                                 void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
     return joint_backward(jp, ws, n_live, grad_scale, G, Hact, bt_idx, bs_idx, kCoefLoss, stream);
+}
+
+RNNTStatus mrnnt_joint_hat_backward(const mrnnt_joint_problem *jp, void *ws, int64_t n_live, const float *grad_scale,
+                                    void *G, void *Hact, int64_t *bt_idx, int64_t *bs_idx, hipStream_t stream) {
+    return joint_backward(jp, ws, n_live, grad_scale, G, Hact, bt_idx, bs_idx, kCoefHat, stream);
 }
 
 RNNTStatus mrnnt_joint_path_workspace_size(const mrnnt_joint_problem *jp, int num_paths, size_t *bytes) {

@@ -198,6 +198,9 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_joint_expect_forward": (i, [JP, vp, sz, vp, vp, i64, i64, vp, vp, i, vp]),
         "mrnnt_joint_expect_rows": (i, [JP, vp, sz, vp, vp, i64, i64, vp, vp, vp, vp]),
         "mrnnt_joint_expect_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp]),
+        "mrnnt_joint_hat_forward": (i, [JP, vp, sz, vp, i, vp]),
+        "mrnnt_joint_hat_backward": (i, [JP, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "mrnnt_joint_hat_align": (i, [JP, vp, sz, vp, i64, vp, vp]),
         "mrnnt_last_error": (ctypes.c_char_p, []),
         "mrnnt_version": (i, []),
         "mrnnt_fill_zero": (i, [vp, sz, vp]),

@@ -60,7 +60,10 @@ def _vp(t: Optional[torch.Tensor]):
 
 class _JointPrepared:
     def __init__(self, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment=None,
-                 max_shift=0):
+                 max_shift=0, hat=False):
+        # hat: the factorised-blank (HAT) calls mrnnt_joint_hat_forward / _align / _backward in place of the softmax
+        # ones; every other call (workspace size, live rows, posteriors, sample, dpre, reduce) is shared
+        self.hat = bool(hat)
         for name, x in (("enc", enc), ("pred", pred), ("weight", weight)):
             if not x.is_cuda:
                 raise RuntimeError(f"monotonic_rnnt_joint: {name} must be a GPU tensor (no CPU implementation)")
@@ -122,8 +125,10 @@ class _JointPrepared:
         with torch.cuda.device(self.device):
             ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
             costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
-            _L.check(lib.mrnnt_joint_forward(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(costs),
-                                             1 if with_beta else 0, self.stream()), "mrnnt_joint_forward")
+            fwd, name = ((lib.mrnnt_joint_hat_forward, "mrnnt_joint_hat_forward") if self.hat
+                         else (lib.mrnnt_joint_forward, "mrnnt_joint_forward"))
+            _L.check(fwd(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(costs), 1 if with_beta else 0,
+                         self.stream()), name)
         return costs, ws
 
     def align(self, L: int):
@@ -135,8 +140,10 @@ class _JointPrepared:
             ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
             out = torch.empty((self.B, L), dtype=torch.int32, device=self.device)
             costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
-            _L.check(lib.mrnnt_joint_align(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(out), L, _vp(costs),
-                                           self.stream()), "mrnnt_joint_align")
+            align, name = ((lib.mrnnt_joint_hat_align, "mrnnt_joint_hat_align") if self.hat
+                           else (lib.mrnnt_joint_align, "mrnnt_joint_align"))
+            _L.check(align(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(out), L, _vp(costs), self.stream()),
+                     name)
         return out, costs
 
     def posteriors(self, label_width: int) -> Posteriors:
@@ -195,8 +202,10 @@ class _JointPrepared:
             if grad_scale is not None:
                 grad_scale = grad_scale.detach().to(self.device, torch.float32).contiguous()
             self.problem.dbias = _vp(dbias)  # the gradient pass adds sum_i G[i] into it (zeroed by the caller)
-            _L.check(lib.mrnnt_joint_backward(ctypes.byref(self.problem), _vp(ws), n, _vp(grad_scale), _vp(G),
-                                              _vp(Hact), _vp(bt), _vp(bs), self.stream()), "mrnnt_joint_backward")
+            bwd, name = ((lib.mrnnt_joint_hat_backward, "mrnnt_joint_hat_backward") if self.hat
+                         else (lib.mrnnt_joint_backward, "mrnnt_joint_backward"))
+            _L.check(bwd(ctypes.byref(self.problem), _vp(ws), n, _vp(grad_scale), _vp(G), _vp(Hact), _vp(bt), _vp(bs),
+                         self.stream()), name)
         if with_index:
             return G[:n], Hact[:n], bt[:n], bs[:n]
         return G[:n], Hact[:n]
@@ -423,21 +432,28 @@ def _split_k_weight_grad(G, Hact, chunks=32):
     return part
 
 
+def _loss_forward(ctx, hat, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment,
+                  max_distance_from_alignment, capturable):
+    """The forward of MonotonicRNNTJointFunction (hat = False) and MonotonicRNNTJointHatFunction (hat = True)."""
+    prep = _JointPrepared(enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment,
+                          max_distance_from_alignment, hat=hat)
+    need = any(ctx.needs_input_grad[:4])
+    costs, ws = prep.forward(with_beta=need)
+    if need:
+        # the workspace is a saved tensor: freed after the last backward, kept under retain_graph=True
+        ctx.save_for_backward(enc, pred, weight, ws)
+        ctx.prep = prep
+        ctx.bias_dtype = None if bias is None else bias.dtype
+        ctx.capturable = capturable
+    return costs
+
+
 class MonotonicRNNTJointFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label=0, alignment=None,
                 max_distance_from_alignment=0, capturable=None):
-        prep = _JointPrepared(enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment,
-                              max_distance_from_alignment)
-        need = any(ctx.needs_input_grad[:4])
-        costs, ws = prep.forward(with_beta=need)
-        if need:
-            # the workspace is a saved tensor: freed after the last backward, kept under retain_graph=True
-            ctx.save_for_backward(enc, pred, weight, ws)
-            ctx.prep = prep
-            ctx.bias_dtype = None if bias is None else bias.dtype
-            ctx.capturable = capturable
-        return costs
+        return _loss_forward(ctx, False, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label,
+                             alignment, max_distance_from_alignment, capturable)
 
     @staticmethod
     def backward(ctx, grad_costs):
@@ -445,6 +461,19 @@ class MonotonicRNNTJointFunction(torch.autograd.Function):
         bias_col, fused_b, db = _dbias_plan(ctx, prep)
         G, Hact = prep.backward_rows(ws, grad_costs, bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
         return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 7
+
+
+class MonotonicRNNTJointHatFunction(MonotonicRNNTJointFunction):
+    """The factorised-blank (HAT) loss under the fused joint, with gradients for enc, pred, weight and bias
+    (mrnnt_joint_hat_forward / mrnnt_joint_live_rows / mrnnt_joint_hat_backward, include/mrnnt.h): the arguments, the
+    dbias plan and the chain from the gradient pass's rows (_grads_from_rows) of MonotonicRNNTJointFunction, whose
+    backward it inherits (the prepared problem calls the factorised-blank gradient pass)."""
+
+    @staticmethod
+    def forward(ctx, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label=0, alignment=None,
+                max_distance_from_alignment=0, capturable=None):
+        return _loss_forward(ctx, True, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label,
+                             alignment, max_distance_from_alignment, capturable)
 
 
 def _capturable(ctx):
@@ -512,6 +541,29 @@ def monotonic_rnnt_joint_loss(enc: torch.Tensor, pred: torch.Tensor, weight: tor
     return MonotonicRNNTJointFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
                                             label_lengths, blank_label, alignment, max_distance_from_alignment,
                                             capturable)
+
+
+def monotonic_rnnt_joint_hat_loss(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
+                                  bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
+                                  label_lengths: torch.Tensor, blank_label: int = 0,
+                                  alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
+                                  capturable: Optional[bool] = None) -> torch.Tensor:
+    """The factorised-blank (HAT, hybrid autoregressive transducer) loss of the joint network
+    tanh(enc + pred) @ weight.T + bias, fused: monotonic_rnnt_hat_loss of the logits monotonic_rnnt_joint_loss never
+    stores. Blank is a Bernoulli on its own logit, log p(blank) = log sigmoid(z_blank), and the labels a softmax over
+    the other V - 1 logits, log p(v) = log sigmoid(-z_blank) + z_v - LSE_{u != blank} z_u -- what internal-LM
+    subtraction needs -- on the fused path: no N x V logits, the same MFMA forward and gradient passes, dweight / dH
+    GEMMs and reduce. Arguments, dtypes, gradients (enc, pred, weight, bias, each in its own dtype), `alignment` /
+    `max_distance_from_alignment` and `capturable` as monotonic_rnnt_joint_loss; non-finite rules as
+    monotonic_rnnt_hat_loss (a NaN / +inf logit or z_blank = +inf in an utterance's band: NaN cost; a label equal to
+    blank_label, a -inf label logit, or a row whose non-blank logits are all -inf: no label arc). An utterance without a
+    path (cost +inf) contributes exactly zero to every gradient, so d_weight / d_bias stay finite for the rest of the
+    batch; a NaN cost keeps NaN gradients. Costs and gradients are bitwise reproducible. monotonic_rnnt_joint_align / _posteriors / _sample take blank_factorized=True for the same
+    distribution; monotonic_rnnt_joint_path_loss / _expected_cost are softmax-only."""
+    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
+    return MonotonicRNNTJointHatFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
+                                               label_lengths, blank_label, alignment, max_distance_from_alignment,
+                                               capturable)
 
 
 class MonotonicRNNTJointPathFunction(torch.autograd.Function):
@@ -674,7 +726,7 @@ def monotonic_rnnt_joint_align(enc: torch.Tensor, pred: torch.Tensor, weight: to
                                bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
                                label_lengths: torch.Tensor, blank_label: int = 0,
                                alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
-                               max_input_length: Optional[int] = None):
+                               max_input_length: Optional[int] = None, blank_factorized: bool = False):
     """Best-path (Viterbi) alignment under the joint network tanh(enc + pred) @ weight.T + bias, without materialising
     its logits (mrnnt_joint_align): monotonic_rnnt_align of the acts monotonic_rnnt_joint_loss never stores. Arguments
     as monotonic_rnnt_joint_loss; `alignment` with `max_distance_from_alignment` restricts the search to the band the
@@ -684,9 +736,10 @@ def monotonic_rnnt_joint_align(enc: torch.Tensor, pred: torch.Tensor, weight: to
     blank_label from T_b on -- what `alignment=` of monotonic_rnnt_joint_loss consumes; costs float32 [B], the negative
     log-probability of that path (>= the loss). L is max T_b, or max_input_length (>= every T_b) when given.
     On a tie the frame emits blank. An utterance without a finite path has cost +inf and its row -1; a NaN / +inf logit
-    in its band gives cost NaN and the row -1. Not differentiable: plain tensors are returned."""
+    in its band gives cost NaN and the row -1. blank_factorized: the best path under the factorised-blank probabilities
+    of monotonic_rnnt_joint_hat_loss (mrnnt_joint_hat_align). Not differentiable: plain tensors are returned."""
     prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
-                          blank_label, alignment, max_distance_from_alignment)
+                          blank_label, alignment, max_distance_from_alignment, hat=blank_factorized)
     L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
     if L < 1:
         raise RuntimeError(f"monotonic_rnnt_joint_align: max_input_length must be >= 1, got {L}")
@@ -697,7 +750,8 @@ def monotonic_rnnt_joint_posteriors(enc: torch.Tensor, pred: torch.Tensor, weigh
                                     bias: Optional[torch.Tensor], labels: torch.Tensor, input_lengths: torch.Tensor,
                                     label_lengths: torch.Tensor, blank_label: int = 0,
                                     alignment: Optional[torch.Tensor] = None,
-                                    max_distance_from_alignment: int = 0) -> Posteriors:
+                                    max_distance_from_alignment: int = 0,
+                                    blank_factorized: bool = False) -> Posteriors:
     """Arc posteriors (the soft alignment) under the joint network, without materialising its logits: the fused
     forward with beta, then mrnnt_joint_posteriors on its workspace. Arguments as monotonic_rnnt_joint_loss; with
     `alignment` the posteriors are those of the restricted distribution.
@@ -706,9 +760,10 @@ def monotonic_rnnt_joint_posteriors(enc: torch.Tensor, pred: torch.Tensor, weigh
     values on the joint's own grid: blank, label [B, enc.size(1), pred.size(1)] (row (b, t, s); 0 for t >= T_b or
     s > S_b), emit [B, enc.size(1)] (0 for t >= T_b), label_time [B, labels.size(1)] (-1 for s >= S_b), costs [B] --
     bit for bit monotonic_rnnt_joint_loss of the same inputs. Rows no path reaches are exactly 0; an utterance
-    without a finite cost has NaN in its own values only. Not differentiable: plain tensors are returned."""
+    without a finite cost has NaN in its own values only. blank_factorized: the posteriors (and costs) of
+    monotonic_rnnt_joint_hat_loss's distribution. Not differentiable: plain tensors are returned."""
     prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
-                          blank_label, alignment, max_distance_from_alignment)
+                          blank_label, alignment, max_distance_from_alignment, hat=blank_factorized)
     return prep.posteriors(labels.size(1) if labels.dim() == 2 else prep.labels.size(1))
 
 
@@ -717,17 +772,18 @@ def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: t
                                 label_lengths: torch.Tensor, num_samples: int, seed: int, first_sample: int = 0,
                                 blank_label: int = 0, alignment: Optional[torch.Tensor] = None,
                                 max_distance_from_alignment: int = 0,
-                                max_input_length: Optional[int] = None) -> Samples:
+                                max_input_length: Optional[int] = None, blank_factorized: bool = False) -> Samples:
     """Alignments drawn from the path posterior under the joint network, without materialising its logits: the fused
     forward with beta, then mrnnt_joint_sample on its workspace. Arguments as monotonic_rnnt_joint_loss plus
     num_samples / seed / first_sample as monotonic_rnnt_sample, whose random numbers and decision rule it shares.
 
     Returns monotonic_rnnt_sample's namedtuple (alignments int32 [B, num_samples, L], path_costs float32
     [B, num_samples], costs float32 [B]); L is max T_b, or max_input_length (>= every T_b) when given. An utterance
-    without a finite cost has its rows -1 and path costs +inf / NaN. Not differentiable: plain tensors are returned."""
+    without a finite cost has its rows -1 and path costs +inf / NaN. blank_factorized: paths from the posterior of
+    monotonic_rnnt_joint_hat_loss's distribution. Not differentiable: plain tensors are returned."""
     K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_joint_sample")
     prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
-                          blank_label, alignment, max_distance_from_alignment)
+                          blank_label, alignment, max_distance_from_alignment, hat=blank_factorized)
     L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
     if L < 1:
         raise RuntimeError(f"monotonic_rnnt_joint_sample: max_input_length must be >= 1, got {L}")
@@ -739,4 +795,4 @@ def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: t
 __all__ = ["MonotonicRNNTJointFunction", "monotonic_rnnt_joint_loss", "monotonic_rnnt_joint_align",
            "monotonic_rnnt_joint_posteriors", "monotonic_rnnt_joint_sample", "MonotonicRNNTJointPathFunction",
            "monotonic_rnnt_joint_path_loss", "MonotonicRNNTJointExpectedCostFunction",
-           "monotonic_rnnt_joint_expected_cost"]
+           "monotonic_rnnt_joint_expected_cost", "MonotonicRNNTJointHatFunction", "monotonic_rnnt_joint_hat_loss"]

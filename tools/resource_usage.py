@@ -15,7 +15,7 @@ cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx9
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
-    m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         continue
     k, v = m.group(1), m.group(2)
@@ -27,6 +27,6 @@ for line in out.splitlines():
         cur[k] = v
 for r in rows:
     if flt in r["name"]:
-        print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("AGPRs","?"):>3} agpr occ {r.get("Occupancy [waves/SIMD]","?"):>2} '
+        print(f'{r.get("VGPRs","?"):>4} vgpr {r.get("AGPRs","?"):>3} agpr {r.get("TotalSGPRs","?"):>3} sgpr occ {r.get("Occupancy [waves/SIMD]","?"):>2} '
               f'sspill {r.get("SGPRs Spill","?"):>3} vspill {r.get("VGPRs Spill","?"):>3} scratch {r.get("ScratchSize [bytes/lane]","?"):>4} '
           f'lds {r.get("LDS Size [bytes/block]","?"):>6}  {r["name"]}')
