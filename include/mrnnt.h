@@ -341,8 +341,9 @@ RNNTStatus mrnnt_expect_backward_tracked(const mrnnt_problem *p, void *workspace
  * bytes. The forward never takes the single-launch (chase) form. mrnnt_posteriors and mrnnt_sample read only lp /
  * alpha / beta / ll and work unchanged on the workspace of mrnnt_hat_forward(with_beta = 1); mrnnt_backward on such a
  * workspace (or mrnnt_hat_backward after mrnnt_forward) is an error the library cannot detect. mrnnt_read_state's and
- * mrnnt_read_denoms' den is -LSE_{v != b} on the rows a factorised forward reduced. The fused joint, mrnnt_path_* and
- * mrnnt_expect_* have no factorised form yet. */
+ * mrnnt_read_denoms' den is -LSE_{v != b} on the rows a factorised forward reduced.
+ * mrnnt_hat_path_* / mrnnt_hat_expect_* (below) are the factorised forms of mrnnt_path_* / mrnnt_expect_* over stored
+ * logits; the fused joint's path scores and expected costs have no factorised form yet. */
 RNNTStatus mrnnt_hat_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, float *costs_dev,
                              int with_beta, hipStream_t stream);
 RNNTStatus mrnnt_hat_backward(const mrnnt_problem *p, const void *workspace, const float *grad_scale, void *grads,
@@ -352,6 +353,52 @@ RNNTStatus mrnnt_hat_backward_tracked(const mrnnt_problem *p, const void *worksp
                                       hipStream_t stream);
 RNNTStatus mrnnt_hat_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out_dev,
                            int64_t out_stride, float *costs_dev, hipStream_t stream);
+
+/* Path scores and expected path costs under the factorised blank (an addition to version 13: MRNNT_VERSION and every
+ * struct are unchanged, callers probe for the symbols mrnnt_hat_path_forward / mrnnt_hat_expect_forward and their
+ * mrnnt_cpu_ twins). Both objectives are -sum_rows (Wb lpb + We lpe) with signed per-row arc weights -- path scores: Wb
+ * / We the summed upstream weights of the valid paths that leave the row by its blank / label arc; expected costs:
+ * Wb = g_c blank_post - g_e cb, We = g_c label_post - g_e ce exactly as mrnnt_expect_backward forms them -- and the
+ * gradient through the factorised row, with den' = -LSE_{u != b} z_u, is
+ *     g[b]      = We sigmoid(z_b) - Wb sigmoid(-z_b)
+ *     g[v != b] = We (exp(z_v + den') - [v == label(s)]).
+ * We is signed and may be exactly 0 while Wb is not (a row visited by blank arcs only): it multiplies the exponential,
+ * it is not folded into the exponent. The blank element is formed once per row from lpb = log sigmoid(z_b), each
+ * sigmoid by itself and the two products in fp64 before one rounding; it is never read off exp(z_b + den'), which
+ * overflows once the blank dominates the row.
+ * Zero rows: a row is stored as exact zeros without reading its acts where Wb == 0 && We == 0 (path scores: in fp64,
+ * so Wb = -We != 0 stays live; expected costs: both fp32 coefficients). Rows outside the hull / band and dead rows are
+ * stored as the softmax entry points store them: 0, or NaN for an utterance of mrnnt_hat_expect_* whose ll is not
+ * finite. A row whose non-blank logits are all -inf (den' = +inf) has no label arc: its non-blank elements are exact
+ * zeros and only g[b] survives. A NaN or +inf logit on a live row (z_b = +inf included) makes the whole row NaN.
+ * Each function takes exactly the arguments, host checks, layouts, element types, device-resident lengths, row state,
+ * workspace size (mrnnt_path_workspace_size / mrnnt_expect_workspace_size serve both) and profile slots of its twin
+ * without _hat; the forwards run the factorised log-softmax (over the hull; mrnnt_hat_forward for the expectation,
+ * never the chase launch), every other forward kernel is the twin's own: the walk, hull, score and coefficient kernels
+ * and the expectation recursion read lp / alpha / beta / den, never a logit. costs_dev of mrnnt_hat_expect_forward is
+ * mrnnt_hat_forward's, bit for bit. A softmax backward on a factorised forward's workspace (or the reverse) is an
+ * error the library cannot detect. */
+RNNTStatus mrnnt_hat_path_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                  const int *alignments_dev, int num_paths, int64_t path_stride, float *path_costs_dev,
+                                  hipStream_t stream);
+RNNTStatus mrnnt_hat_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                   const int *alignments_dev, int num_paths, int64_t path_stride,
+                                   const float *weights_dev, void *grads, hipStream_t stream);
+RNNTStatus mrnnt_hat_path_backward_tracked(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                           const int *alignments_dev, int num_paths, int64_t path_stride,
+                                           const float *weights_dev, void *grads, unsigned char *row_state,
+                                           int64_t row_state_len, hipStream_t stream);
+RNNTStatus mrnnt_hat_expect_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                    const float *blank_cost_dev, const float *label_cost_dev, float *expected_dev,
+                                    float *costs_dev, int with_grad, hipStream_t stream);
+RNNTStatus mrnnt_hat_expect_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                     const float *blank_cost_dev, const float *label_cost_dev,
+                                     const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
+                                     hipStream_t stream);
+RNNTStatus mrnnt_hat_expect_backward_tracked(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                             const float *blank_cost_dev, const float *label_cost_dev,
+                                             const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
+                                             unsigned char *row_state, int64_t row_state_len, hipStream_t stream);
 
 /* Forward log-likelihoods from the workspace (device double [B]), for debugging/inspection:
  * ll_fwd = alpha(T-1, S), ll_bwd = beta(0, 0). Either may be NULL. Asynchronous on `stream`. */
@@ -459,6 +506,22 @@ RNNTStatus mrnnt_cpu_hat_backward(const mrnnt_problem *p, const void *workspace,
                                   int num_threads);
 RNNTStatus mrnnt_cpu_hat_align(const mrnnt_problem *p, void *workspace, size_t workspace_bytes, int *alignment_out,
                                int64_t out_stride, float *costs, int num_threads);
+
+/* mrnnt_hat_path_forward / _backward and mrnnt_hat_expect_forward / _backward for the host implementation: the
+ * arguments, workspace sizes and host checks of mrnnt_cpu_path_* / mrnnt_cpu_expect_*, the formulas, zero-row rule and
+ * den' = +inf rule above in fp64 with the library exp / expm1. grads may be acts itself (in place). */
+RNNTStatus mrnnt_cpu_hat_path_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                      const int *alignments, int num_paths, int64_t path_stride, float *path_costs,
+                                      int num_threads);
+RNNTStatus mrnnt_cpu_hat_path_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                       const int *alignments, int num_paths, int64_t path_stride, const float *weights,
+                                       float *grads, int num_threads);
+RNNTStatus mrnnt_cpu_hat_expect_forward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                        const float *blank_cost, const float *label_cost, float *expected, float *costs,
+                                        int with_grad, int num_threads);
+RNNTStatus mrnnt_cpu_hat_expect_backward(const mrnnt_problem *p, void *workspace, size_t workspace_bytes,
+                                         const float *blank_cost, const float *label_cost, const float *grad_expected,
+                                         const float *grad_costs, float *grads, int num_threads);
 
 /* ---- fused joint network + loss (extension) -------------------------------------
  * The logits are not an input: z(b,t,s,:) = weight * tanh(enc[b,t,:] + pred[b,s,:]) + bias is formed on the

@@ -304,21 +304,10 @@ PathArgs path_args(const PathPlan &pp, void *ws, const int *alignments_dev, int 
                             path_stride);
 }
 
-}  // namespace
-
-extern "C" {
-
-RNNTStatus mrnnt_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    PathPlan pp;
-    const RNNTStatus st = make_path_plan(p, num_paths, &pp);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pp.total;
-    return RNNT_STATUS_SUCCESS;
-}
-
-RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
-                              int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream) {
+// mrnnt_path_forward / mrnnt_hat_path_forward. hat: the factorised-blank log-softmax (DevProblem::hat) over the hull;
+// the walk, hull and score kernels read lp and the band arrays only and serve both.
+RNNTStatus path_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                             int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream, bool hat) {
     PathPlan pp;
     RNNTStatus st = make_path_plan(p, num_paths, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -327,6 +316,7 @@ RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes,
     if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);  // d.min_s / d.max_s: the hull
+    d.hat = hat ? 1 : 0;
     LatticeOpts o;
     o.t_cap = path_stride;
     o.scatter_above = grad_scatter_above(pl);  // the gradient's column order, as mrnnt_forward
@@ -344,16 +334,10 @@ RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes,
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
-                               int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
-                               hipStream_t stream) {
-    return mrnnt_path_backward_tracked(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads,
-                                       nullptr, 0, stream);
-}
-
-RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
-                                       int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
-                                       unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+// mrnnt_path_backward_tracked / mrnnt_hat_path_backward_tracked. hat: the row policy HatPathRows (mrnnt_path.hip).
+RNNTStatus path_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                              int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                              unsigned char *row_state, int64_t row_state_len, hipStream_t stream, bool hat) {
     PathPlan pp;
     RNNTStatus st = make_path_plan(p, num_paths, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -371,13 +355,68 @@ RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t 
     if (e != hipSuccess) return fail_hip(e, "path coefficient kernel");
     d.col_mul = column_order(pl, 2);
     const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    e = timed(K_GRAD, stream, [&] { return launch_path_grad(d, pl.elem, grads, grid, stream); });
+    e = timed(K_GRAD, stream, [&] {
+        return hat ? launch_hat_path_grad(d, pl.elem, grads, grid, stream)
+                   : launch_path_grad(d, pl.elem, grads, grid, stream);
+    });
     if (e != hipSuccess) return fail_hip(e, "path gradient kernel");
     if (pl.pad_S1 != 0) {
         e = launch_pad_zero(d, pl.elem, grads, stream);
         if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
     }
     return RNNT_STATUS_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+RNNTStatus mrnnt_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    PathPlan pp;
+    const RNNTStatus st = make_path_plan(p, num_paths, &pp);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    *bytes = pp.total;
+    return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                              int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream) {
+    return path_forward_impl(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, path_costs_dev, stream, false);
+}
+
+RNNTStatus mrnnt_hat_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                  int num_paths, int64_t path_stride, float *path_costs_dev, hipStream_t stream) {
+    return path_forward_impl(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, path_costs_dev, stream, true);
+}
+
+RNNTStatus mrnnt_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                               int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                               hipStream_t stream) {
+    return mrnnt_path_backward_tracked(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads,
+                                       nullptr, 0, stream);
+}
+
+RNNTStatus mrnnt_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                       int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                                       unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+    return path_backward_impl(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads, row_state,
+                              row_state_len, stream, false);
+}
+
+RNNTStatus mrnnt_hat_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
+                                   int num_paths, int64_t path_stride, const float *weights_dev, void *grads,
+                                   hipStream_t stream) {
+    return path_backward_impl(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads, nullptr, 0,
+                              stream, true);
+}
+
+RNNTStatus mrnnt_hat_path_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes,
+                                           const int *alignments_dev, int num_paths, int64_t path_stride,
+                                           const float *weights_dev, void *grads, unsigned char *row_state,
+                                           int64_t row_state_len, hipStream_t stream) {
+    return path_backward_impl(p, ws, ws_bytes, alignments_dev, num_paths, path_stride, weights_dev, grads, row_state,
+                              row_state_len, stream, true);
 }
 
 }  // extern "C"
@@ -413,6 +452,58 @@ void expect_dev(const ExpectPlan &ep, void *ws, const float *blank_cost_dev, con
     d->ex_we = label_cost_dev;
 }
 
+// mrnnt_expect_forward / mrnnt_hat_expect_forward. hat: the forward is mrnnt_hat_forward's (never the chase launch);
+// the expectation recursion reads alpha / beta / lp and the costs only and serves both.
+RNNTStatus expect_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                               const float *label_cost_dev, float *expected_dev, float *costs_dev, int with_grad,
+                               hipStream_t stream, bool hat) {
+    ExpectPlan ep;
+    RNNTStatus st = make_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    // the loss's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
+    if ((st = forward_impl(p, ws, ws_bytes, costs_dev, with_grad ? 1 : 0, stream, hat)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, ep.pl, ws);
+    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    const hipError_t e =
+        timed(K_DP, stream, [&] { return launch_expect(d, ep.pl.S_max, with_grad ? 1 : 0, expected_dev, stream); });
+    if (e != hipSuccess) return fail_hip(e, "expectation recursion kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
+// mrnnt_expect_backward_tracked / mrnnt_hat_expect_backward_tracked. hat: the row policy HatExpectRows (mrnnt_expect.hip).
+RNNTStatus expect_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                const float *label_cost_dev, const float *grad_expected_dev,
+                                const float *grad_costs_dev, void *grads, unsigned char *row_state,
+                                int64_t row_state_len, hipStream_t stream, bool hat) {
+    ExpectPlan ep;
+    RNNTStatus st = make_expect_plan(p, &ep);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    const Plan &pl = ep.pl;
+    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
+    if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
+    DevProblem d = make_dev(p, pl, ws);
+    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
+    d.row_state = row_state;
+    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    d.ex_ge = grad_expected_dev;
+    d.ex_gc = grad_costs_dev;
+    d.col_mul = column_order(pl, 2);
+    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    hipError_t e = timed(K_GRAD, stream, [&] {
+        return hat ? launch_hat_expect_grad(d, pl.elem, grads, grid, stream)
+                   : launch_expect_grad(d, pl.elem, grads, grid, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "expected-cost gradient kernel");
+    if (pl.pad_S1 != 0) {
+        e = launch_pad_zero(d, pl.elem, grads, stream);
+        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -429,19 +520,15 @@ RNNTStatus mrnnt_expect_workspace_size(const mrnnt_problem *p, size_t *bytes) {
 RNNTStatus mrnnt_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
                                 const float *label_cost_dev, float *expected_dev, float *costs_dev, int with_grad,
                                 hipStream_t stream) {
-    ExpectPlan ep;
-    RNNTStatus st = make_expect_plan(p, &ep);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
-    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
-    // the loss's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
-    if ((st = mrnnt_forward(p, ws, ws_bytes, costs_dev, with_grad ? 1 : 0, stream)) != RNNT_STATUS_SUCCESS) return st;
-    DevProblem d = make_dev(p, ep.pl, ws);
-    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
-    const hipError_t e =
-        timed(K_DP, stream, [&] { return launch_expect(d, ep.pl.S_max, with_grad ? 1 : 0, expected_dev, stream); });
-    if (e != hipSuccess) return fail_hip(e, "expectation recursion kernel");
-    return RNNT_STATUS_SUCCESS;
+    return expect_forward_impl(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, expected_dev, costs_dev, with_grad,
+                               stream, false);
+}
+
+RNNTStatus mrnnt_hat_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                    const float *label_cost_dev, float *expected_dev, float *costs_dev, int with_grad,
+                                    hipStream_t stream) {
+    return expect_forward_impl(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, expected_dev, costs_dev, with_grad,
+                               stream, true);
 }
 
 RNNTStatus mrnnt_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
@@ -455,28 +542,23 @@ RNNTStatus mrnnt_expect_backward_tracked(const mrnnt_problem *p, void *ws, size_
                                          const float *label_cost_dev, const float *grad_expected_dev,
                                          const float *grad_costs_dev, void *grads, unsigned char *row_state,
                                          int64_t row_state_len, hipStream_t stream) {
-    ExpectPlan ep;
-    RNNTStatus st = make_expect_plan(p, &ep);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    const Plan &pl = ep.pl;
-    if ((st = check_pointers(p)) != RNNT_STATUS_SUCCESS) return st;
-    if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
-    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
-    DevProblem d = make_dev(p, pl, ws);
-    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
-    d.row_state = row_state;
-    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
-    d.ex_ge = grad_expected_dev;
-    d.ex_gc = grad_costs_dev;
-    d.col_mul = column_order(pl, 2);
-    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    hipError_t e = timed(K_GRAD, stream, [&] { return launch_expect_grad(d, pl.elem, grads, grid, stream); });
-    if (e != hipSuccess) return fail_hip(e, "expected-cost gradient kernel");
-    if (pl.pad_S1 != 0) {
-        e = launch_pad_zero(d, pl.elem, grads, stream);
-        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
-    }
-    return RNNT_STATUS_SUCCESS;
+    return expect_backward_impl(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, grad_expected_dev, grad_costs_dev,
+                                grads, row_state, row_state_len, stream, false);
+}
+
+RNNTStatus mrnnt_hat_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,
+                                     const float *label_cost_dev, const float *grad_expected_dev,
+                                     const float *grad_costs_dev, void *grads, hipStream_t stream) {
+    return expect_backward_impl(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, grad_expected_dev, grad_costs_dev,
+                                grads, nullptr, 0, stream, true);
+}
+
+RNNTStatus mrnnt_hat_expect_backward_tracked(const mrnnt_problem *p, void *ws, size_t ws_bytes,
+                                             const float *blank_cost_dev, const float *label_cost_dev,
+                                             const float *grad_expected_dev, const float *grad_costs_dev, void *grads,
+                                             unsigned char *row_state, int64_t row_state_len, hipStream_t stream) {
+    return expect_backward_impl(p, ws, ws_bytes, blank_cost_dev, label_cost_dev, grad_expected_dev, grad_costs_dev,
+                                grads, row_state, row_state_len, stream, true);
 }
 
 RNNTStatus mrnnt_read_loglik(const mrnnt_problem *p, const void *ws, double *ll_fwd_dev, double *ll_bwd_dev,

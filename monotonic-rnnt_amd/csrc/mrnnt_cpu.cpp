@@ -612,6 +612,23 @@ void grad_column_hat(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, 
     }
 }
 
+// One factorised-blank row under two signed arc weights (mrnnt_cpu_hat_path_backward / mrnnt_cpu_hat_expect_backward;
+// the HIP path's HatWeightRows, mrnnt_grad.h), in fp64 with the library exp / expm1:
+//   g[blank] = We sigmoid(z_b) - Wb sigmoid(-z_b),   g[v != blank] = We (e^(z_v + den') - [v == label]),
+// sigmoid(z_b) = e^lpb and sigmoid(-z_b) = -expm1(lpb), each by itself. den' = +inf (every label masked): no label arc,
+// the non-blank elements are exact zeros. A NaN lpb (z_b NaN or +inf) makes the whole row NaN. g may be z itself.
+void hat_weight_row(const float *z, float *g, int V, int blank, int label, float den, double lpb, double Wb,
+                    double We) {
+    const float gb = (float)(We * std::exp(lpb) - Wb * -std::expm1(lpb));
+    if (den == std::numeric_limits<float>::infinity() && lpb == lpb) {
+        std::fill(g, g + V, 0.0f);
+    } else {
+        const double d = lpb == lpb ? (double)den : lpb;
+        for (int v = 0; v < V; ++v) g[v] = (float)(We * (std::exp((double)z[v] + d) - (v == label ? 1.0 : 0.0)));
+    }
+    g[blank] = gb;
+}
+
 // Arc posteriors of row (t, s) inside the monotonic band (mrnnt_cpu_posteriors; the HIP path's row_post,
 // mrnnt_posterior.hip): the blank and label corrections of grad_column in fp64,
 //   bp = e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll),  ep = e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll)  (0 at s = S).
@@ -939,8 +956,10 @@ RNNTStatus mrnnt_cpu_path_workspace_size(const mrnnt_problem *p, int num_paths, 
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
-                                  int num_paths, int64_t path_stride, float *path_costs, int num_threads) {
+// mrnnt_cpu_path_forward / mrnnt_cpu_hat_path_forward
+static RNNTStatus cpu_path_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                        int num_paths, int64_t path_stride, float *path_costs, int num_threads,
+                                        bool hat) {
     CpuPathPlan pp;
     RNNTStatus st = make_cpu_path_plan(p, num_paths, alignments, path_stride, false, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -973,7 +992,7 @@ RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *ws, size_t ws_by
         }
         for (int t = 0; t < T; ++t) lo[t] += 1;
     }
-    softmax_pass(p, pl, w, nt);
+    softmax_pass(p, pl, w, nt, hat);
     if (!path_costs) return RNNT_STATUS_SUCCESS;
 #pragma omp parallel for schedule(dynamic, 8) num_threads(nt)
     for (int64_t i = 0; i < (int64_t)pl.B * K; ++i) {
@@ -995,9 +1014,20 @@ RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *ws, size_t ws_by
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
-                                   int num_paths, int64_t path_stride, const float *weights, float *grads,
-                                   int num_threads) {
+RNNTStatus mrnnt_cpu_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                  int num_paths, int64_t path_stride, float *path_costs, int num_threads) {
+    return cpu_path_forward_impl(p, ws, ws_bytes, alignments, num_paths, path_stride, path_costs, num_threads, false);
+}
+
+RNNTStatus mrnnt_cpu_hat_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                      int num_paths, int64_t path_stride, float *path_costs, int num_threads) {
+    return cpu_path_forward_impl(p, ws, ws_bytes, alignments, num_paths, path_stride, path_costs, num_threads, true);
+}
+
+// mrnnt_cpu_path_backward / mrnnt_cpu_hat_path_backward
+static RNNTStatus cpu_path_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                         int num_paths, int64_t path_stride, const float *weights, float *grads,
+                                         int num_threads, bool hat) {
     CpuPathPlan pp;
     RNNTStatus st = make_cpu_path_plan(p, num_paths, alignments, path_stride, false, &pp);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -1045,6 +1075,11 @@ RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_b
                 std::fill(g, g + V, 0.0f);
                 continue;
             }
+            if (hat) {
+                const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != p->blank) ? lab[s] : -1;
+                hat_weight_row(acts + (a0 + s) * V, g, V, p->blank, l, w.den[r0 + s], w.lpb[r0 + s], wb, we);
+                continue;
+            }
             grad_row(acts + (a0 + s) * V, g, V, w.den[r0 + s], (float)(wb + we));
             g[p->blank] -= (float)wb;
             if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)we;
@@ -1052,6 +1087,20 @@ RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_b
     }
     zero_padding_rows(p, pl, grads, V, nt);
     return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                   int num_paths, int64_t path_stride, const float *weights, float *grads,
+                                   int num_threads) {
+    return cpu_path_backward_impl(p, ws, ws_bytes, alignments, num_paths, path_stride, weights, grads, num_threads,
+                                  false);
+}
+
+RNNTStatus mrnnt_cpu_hat_path_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments,
+                                       int num_paths, int64_t path_stride, const float *weights, float *grads,
+                                       int num_threads) {
+    return cpu_path_backward_impl(p, ws, ws_bytes, alignments, num_paths, path_stride, weights, grads, num_threads,
+                                  true);
 }
 
 RNNTStatus mrnnt_cpu_read_state(const mrnnt_problem *p, const void *ws, float *den, double *alpha, double *beta) {
@@ -1164,16 +1213,18 @@ RNNTStatus mrnnt_cpu_expect_workspace_size(const mrnnt_problem *p, size_t *bytes
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
-                                    const float *label_cost, float *expected, float *costs, int with_grad,
-                                    int num_threads) {
+// mrnnt_cpu_expect_forward / mrnnt_cpu_hat_expect_forward
+static RNNTStatus cpu_expect_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                          const float *label_cost, float *expected, float *costs, int with_grad,
+                                          int num_threads, bool hat) {
     CpuExpectPlan ep;
     RNNTStatus st = make_cpu_expect_plan(p, &ep);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const CpuPlan &pl = ep.pl;
     if (!ws || ws_bytes < ep.total)
         return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(ep.total) + " bytes");
-    if ((st = mrnnt_cpu_forward(p, ws, ws_bytes, costs, with_grad ? 1 : 0, num_threads)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = cpu_forward_impl(p, ws, ws_bytes, costs, with_grad ? 1 : 0, num_threads, hat)) != RNNT_STATUS_SUCCESS)
+        return st;
     const Views w = views(pl, ws);
     char *base = static_cast<char *>(ws);
     double *A = reinterpret_cast<double *>(base + ep.off_A), *Bk = reinterpret_cast<double *>(base + ep.off_Bk);
@@ -1193,9 +1244,24 @@ RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_
     return RNNT_STATUS_SUCCESS;
 }
 
-RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
-                                     const float *label_cost, const float *grad_expected, const float *grad_costs,
-                                     float *grads, int num_threads) {
+RNNTStatus mrnnt_cpu_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                    const float *label_cost, float *expected, float *costs, int with_grad,
+                                    int num_threads) {
+    return cpu_expect_forward_impl(p, ws, ws_bytes, blank_cost, label_cost, expected, costs, with_grad, num_threads,
+                                   false);
+}
+
+RNNTStatus mrnnt_cpu_hat_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                        const float *label_cost, float *expected, float *costs, int with_grad,
+                                        int num_threads) {
+    return cpu_expect_forward_impl(p, ws, ws_bytes, blank_cost, label_cost, expected, costs, with_grad, num_threads,
+                                   true);
+}
+
+// mrnnt_cpu_expect_backward / mrnnt_cpu_hat_expect_backward
+static RNNTStatus cpu_expect_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                           const float *label_cost, const float *grad_expected,
+                                           const float *grad_costs, float *grads, int num_threads, bool hat) {
     CpuExpectPlan ep;
     RNNTStatus st = make_cpu_expect_plan(p, &ep);
     if (st != RNNT_STATUS_SUCCESS) return st;
@@ -1247,6 +1313,11 @@ RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *ws, size_t ws
                 std::fill(g, g + V, fin ? 0.0f : std::numeric_limits<float>::quiet_NaN());
                 continue;
             }
+            if (hat) {
+                const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != p->blank) ? lab[s] : -1;
+                hat_weight_row(acts + (a0 + s) * V, g, V, p->blank, l, w.den[r], w.lpb[r], Wb, We);
+                continue;
+            }
             grad_row(acts + (a0 + s) * V, g, V, w.den[r], (float)(Wb + We));
             g[p->blank] -= (float)Wb;
             if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)We;
@@ -1254,6 +1325,20 @@ RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *ws, size_t ws
     }
     zero_padding_rows(p, pl, grads, V, nt);
     return RNNT_STATUS_SUCCESS;
+}
+
+RNNTStatus mrnnt_cpu_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                     const float *label_cost, const float *grad_expected, const float *grad_costs,
+                                     float *grads, int num_threads) {
+    return cpu_expect_backward_impl(p, ws, ws_bytes, blank_cost, label_cost, grad_expected, grad_costs, grads,
+                                    num_threads, false);
+}
+
+RNNTStatus mrnnt_cpu_hat_expect_backward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost,
+                                         const float *label_cost, const float *grad_expected, const float *grad_costs,
+                                         float *grads, int num_threads) {
+    return cpu_expect_backward_impl(p, ws, ws_bytes, blank_cost, label_cost, grad_expected, grad_costs, grads,
+                                    num_threads, true);
 }
 
 }  // extern "C"

@@ -412,7 +412,44 @@ struct ExpectRows : WeightRows {
     }
 };
 
+// The factorised-blank twin (mrnnt_hat_expect_backward, after mrnnt_hat_expect_forward): ExpectRows' band, zero value
+// and weights -- expect_weights reads alpha / beta / lp / A / Bk, never a logit, so it serves unchanged -- with
+// HatWeightRows' slot and formula. Dead where both fp32 weights are zero, as ExpectRows.
+struct HatExpectRows : HatWeightRows {
+    typedef ExpectRows::Col Col;
+    static __device__ __forceinline__ Col column(const DevProblem &p, int b, int64_t c, int t, int T, int S) {
+        return ExpectRows::column(p, b, c, t, T, S);
+    }
+    static __device__ __forceinline__ float zero(const Col &col, float sc) { return ExpectRows::zero(col, sc); }
+
+    static __device__ __forceinline__ Slot stage(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                                 const int *lab_b) {
+        if (!col.fin || !(s >= col.lo && s <= col.hi)) return dead();
+        const int64_t row = rowc + s;
+        const RowInMemory r{p, t, S, s, S + 1, row, col.arow, t == col.T - 1};
+        const ArcWeights w = expect_weights(r, s < S, col.ll, col.R, col.ge, col.gc);
+        if ((float)w.wb == 0.0f && (float)w.we == 0.0f) return dead();  // exact zeros, acts not read
+        return weight_slot(p, S, s, row, w.wb, w.we, lab_b);
+    }
+    static __device__ __forceinline__ bool row(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                               const int *lab_b, Coef &c) {
+        const Slot cf = stage(p, col, t, S, s, rowc, lab_b);
+        c = coef(cf);
+        return live(cf);
+    }
+
+    static constexpr bool kNtLoads = true;
+    template <class IO, bool NTL, bool NTS, int U>
+    static void launch_u(const DevProblem &p, const float *, void *grads, int grid, hipStream_t stream) {
+        grad_staged_kernel<IO, U, staged_rows(U), NTL, NTS, HatExpectRows><<<grid, 256, 0, stream>>>(p, nullptr, grads);
+    }
+};
+
 }  // namespace
+
+hipError_t launch_hat_expect_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream) {
+    return launch_grad_rows<HatExpectRows>(p, elem, nullptr, grads, grid, stream);
+}
 
 hipError_t launch_expect(const DevProblem &p, int S_max, int with_bk, float *expected, hipStream_t stream) {
     if (!launch_by_width<true>(S_max + 1, ExpectLaunch{p, with_bk, expected, stream})) return hipErrorInvalidValue;

@@ -1,6 +1,7 @@
 // mrnnt_grad.h -- the dense logit-gradient streamers and their launch ladder, over a compile-time row policy P: the
 // loss gradient (LossRows, mrnnt_grad.hip), the path-score gradient (PathRows, mrnnt_path.hip), the expected-cost
-// gradient (ExpectRows, mrnnt_expect.hip) and the factorised-blank loss gradient (HatRows, mrnnt_hat.hip). P supplies
+// gradient (ExpectRows, mrnnt_expect.hip), the factorised-blank loss gradient (HatRows, mrnnt_hat.hip) and the
+// factorised-blank twins of the path-score and expected-cost gradients (HatPathRows, HatExpectRows). P supplies
 //   Col, column()   what a lattice column sets up once: its band of rows with a gradient; zero(): the other rows' value
 //   Slot, stage()   a row's coefficients as they are staged in LDS, two buffers of 256 slots (a dead slot: the row is
 //                   stored as zero()), live(); skip() / skipped(): a dead slot whose row already holds zero() (row state)
@@ -207,6 +208,72 @@ struct WeightRows {
         float g = rc.wocc * fast_exp2(fmaf(z, kLog2e, rc.c2));
         if (v == blank) g -= rc.cb;
         else if (v == rc.lab) g -= rc.ce;
+        return g;
+    }
+};
+
+// The same two signed arc weights over a factorised-blank row (after a forward with p.hat: den = den' = -LSE over the
+// non-blank logits, lp.b = log sigmoid(z_blank)) -- HatPathRows, mrnnt_path.hip; HatExpectRows, mrnnt_expect.hip:
+//   g[blank]      = We sigmoid(z_b) - Wb sigmoid(-z_b)
+//   g[v != blank] = We (exp(z_v + den') - [v == label(s)])
+// HatRows' formula (mrnnt_hat.hip) with the posteriors replaced by the weights. We is signed and may be exactly 0 while
+// Wb is not, so it cannot go into the exponent as log We: the slot carries the multiplier itself, still one float4.
+// The blank element is a select on the row's gb, never arithmetic on exp(z_b + den'), which overflows once the blank
+// dominates the row (0 * inf). The policy adds Col / column() / zero() / stage() / row() / launch_u().
+struct HatWeightRows {
+    typedef float4 Slot;  // {c2, We, gb, label | kDeadRow | kSkipRow}
+    struct Coef {
+        float c2;  // den' * log2(e); -inf where den' = +inf (every label masked: the non-blank elements are exact zeros)
+        float we;  // We
+        float gb;  // the blank element
+        int lab;   // label(s), -1 for s == S / label == blank / out of range
+    };
+    static __device__ __forceinline__ Slot dead() { return make_float4(0.0f, 0.0f, 0.0f, __int_as_float(kDeadRow)); }
+    static __device__ __forceinline__ bool live(const Slot &cf) { return __float_as_int(cf.w) > kDeadRow; }
+    static __device__ __forceinline__ void skip(Slot &cf) { cf.w = __int_as_float(kSkipRow); }
+    static __device__ __forceinline__ bool skipped(const Slot &cf) { return __float_as_int(cf.w) == kSkipRow; }
+    static __device__ __forceinline__ Coef coef(const Slot &cf) {
+        return Coef{cf.x, cf.y, cf.z, __float_as_int(cf.w)};
+    }
+
+    // The slot of a live row from its fp64 weights. gb as hat_coef (mrnnt_hat.h) forms it, once per row from
+    // lpb = lp[row].b: sigmoid(z_b) = exp(lpb), sigmoid(-z_b) = -expm1(lpb) near 0 and 1 - exp(lpb) elsewhere, each
+    // by itself (never (Wb + We) sigmoid(z_b) - Wb); the two products in fp64 from the fp64 weights, one rounding.
+    static __device__ __forceinline__ Slot weight_slot(const DevProblem &p, int S, int s, int64_t row, double wb,
+                                                       double we, const int *lab_b) {
+        const float den = p.den[row];
+        const float q = (float)p.lp[row].b;
+        const float sp = fast_exp2(q * kLog2e);
+        const float sn = q > -0.5f ? -expm1f(q) : 1.0f - sp;
+        const float gb = (float)(we * (double)sp - wb * (double)sn);
+        const bool masked = den == -NEG_INF_F;  // no label arc: only gb survives
+        float c2 = masked ? NEG_INF_F : den * kLog2e;
+        if (q != q) c2 = q;  // a NaN (or +inf) blank logit: the whole row is NaN, as its lp pair is
+        const int lab = masked ? -1 : WeightRows::slot_label(p, S, s, lab_b);
+        return make_float4(c2, (float)we, gb, __int_as_float(lab));
+    }
+
+    template <class IO>
+    static __device__ __forceinline__ typename IO::V grad_vec(const typename IO::V &xv, const Coef &rc, int j, int blank,
+                                                              float) {
+        constexpr int E = IO::E;
+        float x[E];
+        IO::unpack(xv, x);
+        const int v0 = j * E;
+        const int db = blank - v0;
+        const int de = rc.lab >= 0 ? rc.lab - v0 : -1;
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            float g = rc.we * fast_exp2(fmaf(x[i], kLog2e, rc.c2));
+            g -= de == i ? rc.we : 0.0f;
+            x[i] = db == i ? rc.gb : g;
+        }
+        return IO::pack(x);
+    }
+    static __device__ __forceinline__ float grad(float z, int v, const Coef &rc, int blank, float) {
+        float g = rc.we * fast_exp2(fmaf(z, kLog2e, rc.c2));
+        if (v == blank) g = rc.gb;
+        else if (v == rc.lab) g -= rc.we;
         return g;
     }
 };

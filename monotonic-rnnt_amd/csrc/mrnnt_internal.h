@@ -332,6 +332,8 @@ hipError_t launch_path_walk(const DevProblem &p, const PathArgs &a, int T_bound,
 hipError_t launch_path_score(const DevProblem &p, const PathArgs &a, hipStream_t stream);
 hipError_t launch_path_coef(const DevProblem &p, const PathArgs &a, int T_bound, hipStream_t stream);
 hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
+// ... after a forward with p.hat over the hull (mrnnt_hat_path_*): the row policy HatPathRows
+hipError_t launch_hat_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
 
 // mrnnt_expect_forward / mrnnt_expect_backward (mrnnt_expect.hip): the first-order expectation recursion over the
 // state of a forward (p.ex_A forward in time and, with_bk, p.ex_Bk backward, one workgroup per utterance and
@@ -339,6 +341,8 @@ hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid
 // of g_e . expected + g_c . costs over the row policy ExpectRows.
 hipError_t launch_expect(const DevProblem &p, int S_max, int with_bk, float *expected, hipStream_t stream);
 hipError_t launch_expect_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
+// ... after a factorised-blank forward (mrnnt_hat_expect_*): the row policy HatExpectRows
+hipError_t launch_hat_expect_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream);
 // mrnnt_joint_expect_rows: the same two row weights Wb / We (fp64, ExpectRows' own function) of every row of the
 // monotonic band into wb_out / we_out [N] -- exact 0.0 where both round to fp32 zeros, NaN for a non-finite ll -- for
 // launch_row_list mode 3 and launch_joint_backward(path_coef) on a device problem whose alpha / beta point at them.

@@ -18,6 +18,9 @@
 //                                       so no atomics and a fixed order
 //   grad                                the gradient streamers of mrnnt_grad.h over PathRows: coefficients from Wb /
 //                                       We / den; "in band" = in the hull, "live" = Wb != 0 || We != 0
+// The factorised blank (mrnnt_hat_path_*): the same walk, hull, score and coef kernels -- they read lp / alpha / beta /
+// the band arrays, never a logit -- around the HAT flavour of the log-softmax (p.hat) and the gradient over
+// HatPathRows, g[blank] = We sigmoid(z_b) - Wb sigmoid(-z_b), g[v != blank] = We (exp(z_v + den') - [v == label(s)]).
 //
 // The hull in the band arrays. The log-softmax reduces, in column c = (b, t), the rows
 //   [min(min_s[c] - 1, min_s[c-1]), max(max_s[c], max_s[c-1])]        (align_window, mrnnt_device.h; t = 0: with 0)
@@ -226,6 +229,38 @@ struct PathRows : WeightRows {
     }
 };
 
+// The factorised-blank twin (mrnnt_hat_path_backward, after a forward with p.hat over the hull): PathRows' band, zero
+// value and liveness rule (Wb != 0 || We != 0 in fp64: Wb = -We stays live), HatWeightRows' slot and formula.
+struct HatPathRows : HatWeightRows {
+    typedef PathRows::Col Col;
+    static __device__ __forceinline__ Col column(const DevProblem &p, int b, int64_t c, int t, int T, int S) {
+        return PathRows::column(p, b, c, t, T, S);
+    }
+    static __device__ __forceinline__ float zero(const Col &, float) { return 0.0f; }
+
+    static __device__ __forceinline__ Slot stage(const DevProblem &p, const Col &col, int, int S, int s, int64_t rowc,
+                                                 const int *lab_b) {
+        if (!(s >= col.lo && s <= col.hi)) return dead();
+        const int64_t row = rowc + s;
+        const double wb = p.alpha[row], we = p.beta[row];
+        if (!(wb != 0.0 || we != 0.0)) return dead();
+        return weight_slot(p, S, s, row, wb, we, lab_b);
+    }
+    static __device__ __forceinline__ bool row(const DevProblem &p, const Col &col, int t, int S, int s, int64_t rowc,
+                                               const int *lab_b, Coef &c) {
+        const Slot cf = stage(p, col, t, S, s, rowc, lab_b);
+        c = coef(cf);
+        return live(cf);
+    }
+
+    static constexpr bool kNtLoads = false;
+    template <class IO, bool NTL, bool NTS, int U>
+    static void launch_u(const DevProblem &p, const float *, void *grads, int grid, hipStream_t stream) {
+        static_assert(!NTL, "path scores never load nontemporally");
+        grad_staged_kernel<IO, U, staged_rows(U), false, NTS, HatPathRows><<<grid, 256, 0, stream>>>(p, nullptr, grads);
+    }
+};
+
 // x workgroups of 4 waves per utterance for the (utterance, frame block) kernels
 dim3 block_grid(const DevProblem &p, int T_bound) {
     const int blocks = std::max(1, (T_bound + 63) / 64);
@@ -255,6 +290,10 @@ hipError_t launch_path_coef(const DevProblem &p, const PathArgs &a, int T_bound,
 
 hipError_t launch_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream) {
     return launch_grad_rows<PathRows>(p, elem, nullptr, grads, grid, stream);
+}
+
+hipError_t launch_hat_path_grad(const DevProblem &p, int elem, void *grads, int grid, hipStream_t stream) {
+    return launch_grad_rows<HatPathRows>(p, elem, nullptr, grads, grid, stream);
 }
 
 }  // namespace mrnnt

@@ -177,6 +177,16 @@ def _bind(path: str, dev: bool = False) -> ctypes.CDLL:
         "mrnnt_cpu_hat_forward": (i, [P, vp, sz, vp, i, i]),
         "mrnnt_cpu_hat_backward": (i, [P, vp, vp, vp, i]),
         "mrnnt_cpu_hat_align": (i, [P, vp, sz, vp, i64, vp, i]),
+        "mrnnt_hat_path_forward": (i, [P, vp, sz, vp, i, i64, vp, vp]),
+        "mrnnt_hat_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, vp]),
+        "mrnnt_hat_path_backward_tracked": (i, [P, vp, sz, vp, i, i64, vp, vp, vp, i64, vp]),
+        "mrnnt_cpu_hat_path_forward": (i, [P, vp, sz, vp, i, i64, vp, i]),
+        "mrnnt_cpu_hat_path_backward": (i, [P, vp, sz, vp, i, i64, vp, vp, i]),
+        "mrnnt_hat_expect_forward": (i, [P, vp, sz, vp, vp, vp, vp, i, vp]),
+        "mrnnt_hat_expect_backward": (i, [P, vp, sz, vp, vp, vp, vp, vp, vp]),
+        "mrnnt_hat_expect_backward_tracked": (i, [P, vp, sz, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "mrnnt_cpu_hat_expect_forward": (i, [P, vp, sz, vp, vp, vp, vp, i, i]),
+        "mrnnt_cpu_hat_expect_backward": (i, [P, vp, sz, vp, vp, vp, vp, vp, i]),
         "mrnnt_joint_workspace_size": (i, [JP, ctypes.POINTER(sz)]),
         "mrnnt_joint_forward": (i, [JP, vp, sz, vp, i, vp]),
         "mrnnt_joint_align": (i, [JP, vp, sz, vp, i64, vp, vp]),

@@ -479,8 +479,8 @@ def monotonic_rnnt_hat_loss(acts: torch.Tensor, labels: torch.Tensor, input_leng
     suppressed blank logit loses no digits. A -inf label logit or blank logit means "no such arc"; a NaN or +inf
     logit in an utterance's band (the blank logit included) gives that utterance a NaN cost and leaves the others
     bit-identical. Returns float32 costs [B] on acts.device. The read-outs take blank_factorized=True
-    (monotonic_rnnt_align / _posteriors / _sample); the fused joint, monotonic_rnnt_path_loss and
-    monotonic_rnnt_expected_cost are softmax-only for now."""
+    (monotonic_rnnt_align / _posteriors / _sample), and so do monotonic_rnnt_path_loss and monotonic_rnnt_expected_cost;
+    the fused joint's path scores and expected costs are softmax-only for now."""
     result = MonotonicRNNTHatFunction.apply(acts, labels, input_lengths, label_lengths, alignment,
                                             max_distance_from_alignment, blank_label)
     assert result is not None
@@ -633,12 +633,15 @@ def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_length
 class MonotonicRNNTPathFunction(torch.autograd.Function):
     """Scores of given alignments with their logit gradient (mrnnt_path_forward / mrnnt_path_backward and the
     mrnnt_cpu_path_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, alignments,
-    blank_label=0) -> path_costs [B, K]. The upstream gradient of path_costs is the kernels' weights w[b, k]."""
+    blank_label=0, blank_factorized=False) -> path_costs [B, K]. The upstream gradient of path_costs is the kernels'
+    weights w[b, k]. blank_factorized: the mrnnt_hat_path_* / mrnnt_cpu_hat_path_* entry points."""
 
     @staticmethod
     def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
-                label_lengths: torch.Tensor, alignments: torch.Tensor, blank_label: int = 0) -> torch.Tensor:
+                label_lengths: torch.Tensor, alignments: torch.Tensor, blank_label: int = 0,
+                blank_factorized: bool = False) -> torch.Tensor:
         prep = _Prepared(acts, labels, input_lengths, label_lengths, None, 0, blank_label)
+        hat = "hat_" if blank_factorized else ""
         B, dev = prep.problem.B, prep.device
         al = alignments.detach()
         if al.device != dev or al.dtype != torch.int32:
@@ -651,34 +654,35 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
             raise RuntimeError(f"monotonic_rnnt_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got {K}, {L}")
         ws = prep.workspace(num_paths=K)
         costs = torch.empty((B, K), dtype=torch.float32, device=dev)
-        _call(prep, "path_forward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(costs), pending=True)
+        _call(prep, hat + "path_forward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(costs), pending=True)
         if ctx.needs_input_grad[0]:
             # acts is re-read by the gradient kernel on the rows the paths visit; the workspace holds den, the hull
             # and the paths' validity
             ctx.save_for_backward(acts, ws, al)
-            ctx.prep = prep
+            ctx.prep, ctx.hat = prep, hat
         return costs
 
     @staticmethod
     def backward(ctx, grad_costs):
         _, ws, al = ctx.saved_tensors
-        prep = ctx.prep
+        prep, hat = ctx.prep, ctx.hat
         K, L = al.size(1), al.size(2)
         w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
         # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), as the loss's
         grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
         if ticket is not None:  # (the row state, as the loss's _backward)
-            _call(prep, "path_backward_tracked", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
+            _call(prep, hat + "path_backward_tracked", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
                   _ptr(ticket.state), ticket.state.numel(), lengths=False)
             ticket.commit()
         else:
-            _call(prep, "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads), lengths=False)
-        return grads, None, None, None, None, None
+            _call(prep, hat + "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
+                  lengths=False)
+        return grads, None, None, None, None, None, None
 
 
 def monotonic_rnnt_path_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                              label_lengths: torch.Tensor, alignments: torch.Tensor,
-                             blank_label: int = 0) -> torch.Tensor:
+                             blank_label: int = 0, blank_factorized: bool = False) -> torch.Tensor:
     """Differentiable scores of given alignments: path_costs[b, k] = -log p(alignment (b, k) | acts), the negative
     log-probability of that one path through the lattice the loss sums over, with a gradient with respect to acts.
     The missing piece between the read-outs (monotonic_rnnt_align, monotonic_rnnt_sample: not differentiable) and
@@ -700,12 +704,17 @@ def monotonic_rnnt_path_loss(acts: torch.Tensor, labels: torch.Tensor, input_len
     logit on a visited row makes the visiting paths' costs and that row's gradient NaN and nothing else. Rows no valid
     path with a non-zero upstream gradient visits have an exactly zero gradient and are not read. Costs and gradients
     are bitwise reproducible. GPU-resident lengths that fail validation (T_b <= L included) make every value NaN and
-    surface through check_lengths() exactly as for the loss."""
+    surface through check_lengths() exactly as for the loss.
+    blank_factorized=True: the scores and their gradient under monotonic_rnnt_hat_loss's distribution (blank a Bernoulli
+    on its own logit, the labels a softmax over the others) -- the distribution that monotonic_rnnt_sample / _align
+    (blank_factorized=True) draw and search under -- with the same kernels around a factorised log-softmax and gradient
+    pass; a row whose non-blank logits are all -inf has no label arc and only its blank element gets a gradient."""
     if alignments.dim() == 2:
         out = MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments.unsqueeze(1),
-                                              blank_label)
+                                              blank_label, blank_factorized)
         return out.squeeze(1)
-    return MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments, blank_label)
+    return MonotonicRNNTPathFunction.apply(acts, labels, input_lengths, label_lengths, alignments, blank_label,
+                                           blank_factorized)
 
 
 def _cost_array(x: Optional[torch.Tensor], prep: _Prepared, what: str) -> Optional[torch.Tensor]:
@@ -726,16 +735,18 @@ def _upstream(g: Optional[torch.Tensor], prep: _Prepared) -> Optional[torch.Tens
 class MonotonicRNNTExpectedCostFunction(torch.autograd.Function):
     """Expected path costs and the loss with their logit gradient (mrnnt_expect_forward / mrnnt_expect_backward and the
     mrnnt_cpu_expect_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, blank_costs,
-    label_costs, alignment=None, max_distance_from_alignment=0, blank_label=0) -> (expected [B], costs [B]). The two
-    upstream gradients go into one backward call that writes one gradient buffer."""
+    label_costs, alignment=None, max_distance_from_alignment=0, blank_label=0, blank_factorized=False) ->
+    (expected [B], costs [B]). The two upstream gradients go into one backward call that writes one gradient buffer.
+    blank_factorized: the mrnnt_hat_expect_* / mrnnt_cpu_hat_expect_* entry points."""
 
     @staticmethod
     def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                 label_lengths: torch.Tensor, blank_costs: Optional[torch.Tensor] = None,
                 label_costs: Optional[torch.Tensor] = None, alignment: Optional[torch.Tensor] = None,
-                max_distance_from_alignment: int = 0, blank_label: int = 0):
+                max_distance_from_alignment: int = 0, blank_label: int = 0, blank_factorized: bool = False):
         prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
                          blank_label)
+        hat = "hat_" if blank_factorized else ""
         wb = _cost_array(blank_costs, prep, "blank_costs")
         we = _cost_array(label_costs, prep, "label_costs")
         need_grad = bool(ctx.needs_input_grad[0])
@@ -743,36 +754,36 @@ class MonotonicRNNTExpectedCostFunction(torch.autograd.Function):
         B, dev = prep.problem.B, prep.device
         expected = torch.empty(B, dtype=torch.float32, device=dev)
         costs = torch.empty(B, dtype=torch.float32, device=dev)
-        _call(prep, "expect_forward", _ptr(ws), ws.numel(), _ptr(wb), _ptr(we), _ptr(expected), _ptr(costs),
+        _call(prep, hat + "expect_forward", _ptr(ws), ws.numel(), _ptr(wb), _ptr(we), _ptr(expected), _ptr(costs),
               1 if need_grad else 0, pending=True)
         if need_grad:
             # acts is re-read by the gradient kernel; the workspace holds the loss's state and A / Bk / R
             ctx.save_for_backward(acts, ws)
-            ctx.prep, ctx.wb, ctx.we = prep, wb, we
+            ctx.prep, ctx.wb, ctx.we, ctx.hat = prep, wb, we, hat
         return expected, costs
 
     @staticmethod
     def backward(ctx, grad_expected, grad_costs):
         _, ws = ctx.saved_tensors
-        prep = ctx.prep
+        prep, hat = ctx.prep, ctx.hat
         ge, gc = _upstream(grad_expected, prep), _upstream(grad_costs, prep)
         # the tracked, placement-probed buffer of the loss's backward (_grads_placement)
         grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
         if ticket is not None:
-            _call(prep, "expect_backward_tracked", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
-                  _ptr(grads), _ptr(ticket.state), ticket.state.numel(), lengths=False)
+            _call(prep, hat + "expect_backward_tracked", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge),
+                  _ptr(gc), _ptr(grads), _ptr(ticket.state), ticket.state.numel(), lengths=False)
             ticket.commit()
         else:
-            _call(prep, "expect_backward", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
+            _call(prep, hat + "expect_backward", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
                   _ptr(grads), lengths=False)
-        return grads, None, None, None, None, None, None, None, None
+        return grads, None, None, None, None, None, None, None, None, None
 
 
 def monotonic_rnnt_expected_cost(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                                  label_lengths: torch.Tensor, blank_costs: Optional[torch.Tensor] = None,
                                  label_costs: Optional[torch.Tensor] = None,
                                  alignment: Optional[torch.Tensor] = None, max_distance_from_alignment: int = 0,
-                                 blank_label: int = 0):
+                                 blank_label: int = 0, blank_factorized: bool = False):
     """The exact expectation, under the path posterior p(path | labels, acts) of the lattice the loss sums over, of a
     cost that adds up over the arcs of a path -- and the loss of the same inputs -- both differentiable with respect to
     acts (the first-order expectation semiring: one more recursion over the forward's state, no sampling):
@@ -801,9 +812,12 @@ def monotonic_rnnt_expected_cost(acts: torch.Tensor, labels: torch.Tensor, input
     exactly zero gradient and are not read. An utterance without a finite cost has a NaN expected value and NaN gradient
     rows; the others are unaffected. Results are bitwise reproducible and do not depend on the other utterances.
     GPU-resident lengths that fail validation make every value NaN and surface through check_lengths() as for the
-    loss."""
+    loss.
+    blank_factorized=True: the expectation, the costs (monotonic_rnnt_hat_loss's, bit-identical) and the gradient under
+    the factorised-blank distribution of monotonic_rnnt_hat_loss -- the expected-latency regulariser of a HAT model."""
     return MonotonicRNNTExpectedCostFunction.apply(acts, labels, input_lengths, label_lengths, blank_costs, label_costs,
-                                                   alignment, max_distance_from_alignment, blank_label)
+                                                   alignment, max_distance_from_alignment, blank_label,
+                                                   blank_factorized)
 
 
 class MonotonicRNNTLoss(torch.nn.Module):
