@@ -81,14 +81,21 @@ class Dev:
     def lengths(self, T, S, device_lengths):
         return (self.t(T), self.t(S)) if device_lengths else (torch.from_numpy(T), torch.from_numpy(S))
 
-    def acts(self, acts, dtype=None):
+    def acts(self, acts, dtype=None, unaligned=False, grads=True):
         a = self.t(acts)
-        return (a if dtype is None else a.to(dtype)).requires_grad_(True)
+        a = a if dtype is None else a.to(dtype)
+        if unaligned:  # rows that start 4 bytes past a 16-byte boundary: the scalar kernels
+            n = 4 // a.element_size()
+            buf = torch.empty(a.numel() + n, dtype=a.dtype, device=self.device)
+            buf[n:].copy_(a.reshape(-1))
+            a = buf[n:].view(a.shape)
+            assert a.data_ptr() % 16 == 4 and a.is_contiguous()
+        return a.requires_grad_(grads)
 
-    def path(self, acts, labels, T, S, al, w, blank, hat=True, dtype=None, device_lengths=False):
+    def path(self, acts, labels, T, S, al, w, blank, hat=True, dtype=None, device_lengths=False, unaligned=False):
         """(path_costs fp32 [B, K], grads fp32 in the shape of acts)"""
         import monotonic_rnnt_op as op
-        a = self.acts(acts, dtype)
+        a = self.acts(acts, dtype, unaligned)
         Tt, St = self.lengths(T, S, device_lengths)
         kw = {"blank_factorized": True} if hat else {}
         pc = op.monotonic_rnnt_path_loss(a, self.t(labels), Tt, St, self.t(al), blank_label=blank, **kw)
@@ -98,10 +105,10 @@ class Dev:
         return pc.detach().cpu().numpy(), a.grad.float().cpu().numpy()
 
     def expect(self, acts, labels, T, S, wb, we, ge, gc, blank, alignment=None, k=0, hat=True, dtype=None,
-               device_lengths=False):
+               device_lengths=False, unaligned=False):
         """(expected fp32 [B], costs fp32 [B], grads fp32 in the shape of acts)"""
         import monotonic_rnnt_op as op
-        a = self.acts(acts, dtype)
+        a = self.acts(acts, dtype, unaligned)
         Tt, St = self.lengths(T, S, device_lengths)
         kw = {"blank_factorized": True} if hat else {}
         e, c = op.monotonic_rnnt_expected_cost(a, self.t(labels), Tt, St, self.t(wb), self.t(we), self.t(alignment), k,
@@ -113,12 +120,20 @@ class Dev:
                                          self.t(one if gc is None else np.asarray(gc, np.float32))))
         return e.detach().cpu().numpy(), c.detach().cpu().numpy(), a.grad.float().cpu().numpy()
 
-    def hat_loss(self, acts, labels, T, S, gc, blank):
+    def hat_loss(self, acts, labels, T, S, gc, blank, alignment=None, k=0, dtype=None, device_lengths=False,
+                 unaligned=False):
+        """(costs fp32 [B], grads fp64 in the shape of acts -- 2-D packed or 4-D padded) of monotonic_rnnt_hat_loss
+        with the per-utterance upstream gradient gc; gc None: the cost-only forward, (costs, None)."""
         import monotonic_rnnt_op as op
-        a = self.acts(acts)
-        c = op.monotonic_rnnt_hat_loss(a, self.t(labels), torch.from_numpy(T), torch.from_numpy(S), None, 0, blank)
+        a = self.acts(acts, dtype, unaligned, grads=gc is not None)
+        Tt, St = self.lengths(T, S, device_lengths)
+        c = op.monotonic_rnnt_hat_loss(a, self.t(labels), Tt, St, self.t(alignment), k, blank)
+        assert c.dtype == torch.float32 and c.shape == (len(T),)
+        if gc is None:
+            return c.detach().cpu().numpy(), None
         c.backward(self.t(np.asarray(gc, np.float32)))
-        return c.detach().cpu().numpy(), a.grad.cpu().numpy().astype(np.float64)
+        assert a.grad.dtype == a.dtype and a.grad.shape == a.shape
+        return c.detach().cpu().numpy(), a.grad.float().cpu().numpy().astype(np.float64)
 
     def readout(self, name, acts, labels, T, S, blank, *args, **kw):
         import monotonic_rnnt_op as op

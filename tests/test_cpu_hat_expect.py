@@ -24,7 +24,7 @@ def test_non_finite_logits(V, blank):
     C.check_expect_non_finite(DEV, V, blank)
 
 
-@pytest.mark.parametrize("V,blank", [(5, 2), (64, 63)])
+@pytest.mark.parametrize("V,blank", [(5, 2), (64, 63), (100, 98), (1028, 1024)])
 def test_consistency_with_posteriors_and_the_hat_loss(V, blank):
     C.check_expect_consistency(DEV, V, blank)
 

@@ -35,7 +35,7 @@ def test_non_finite_logits(V, blank):
     C.check_path_non_finite(DEV, V, blank)
 
 
-@pytest.mark.parametrize("V,blank", [(5, 4), (64, 0)])
+@pytest.mark.parametrize("V,blank", [(5, 4), (64, 0), (100, 98), (1028, 1024)])
 def test_consistency_with_sample_and_align(V, blank):
     C.check_path_consistency(DEV, V, blank)
 

@@ -47,7 +47,7 @@ def test_non_finite_logits(dev, V, blank):
     C.check_expect_non_finite(dev, V, blank)
 
 
-@pytest.mark.parametrize("V,blank", [(5, 2), (64, 63), (1024, 767)])
+@pytest.mark.parametrize("V,blank", [(5, 2), (64, 63), (1024, 767), (100, 98), (1028, 1024)])
 def test_consistency_with_posteriors_and_the_hat_loss(dev, V, blank):
     C.check_expect_consistency(dev, V, blank)
 
