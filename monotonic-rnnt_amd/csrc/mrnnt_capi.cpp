@@ -53,6 +53,34 @@ bool copy_out(void *dst, const void *src, size_t bytes, hipStream_t stream) {
     return !dst || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream) == hipSuccess;
 }
 
+// The tail of every dense gradient entry point, after its own checks: the row state, `before` (what the caller still
+// launches ahead of the pass), the pass's column order, launch(d, grid) counted under K_GRAD ("<what> kernel" on
+// failure), then the padding rows of the padded layout. grid 0: the persistent grid over the plan's columns.
+template <class Launch, class Before>
+RNNTStatus gradient_pass(const Plan &pl, DevProblem &d, unsigned char *row_state, int64_t row_state_len, void *grads,
+                         int grid, const char *what, hipStream_t stream, Launch &&launch, Before &&before) {
+    RNNTStatus st = check_row_state(d, row_state, row_state_len);
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    d.row_state = row_state;
+    if ((st = before()) != RNNT_STATUS_SUCCESS) return st;
+    d.col_mul = column_order(pl, 2);
+    if (grid == 0) grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
+    hipError_t e = timed(K_GRAD, stream, [&] { return launch(d, grid); });
+    if (e != hipSuccess) return fail_hip(e, what);
+    if (pl.pad_S1 != 0) {
+        e = launch_pad_zero(d, pl.elem, grads, stream);
+        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
+    }
+    return RNNT_STATUS_SUCCESS;
+}
+
+template <class Launch>
+RNNTStatus gradient_pass(const Plan &pl, DevProblem &d, unsigned char *row_state, int64_t row_state_len, void *grads,
+                         int grid, const char *what, hipStream_t stream, Launch &&launch) {
+    return gradient_pass(pl, d, row_state, row_state_len, grads, grid, what, stream, launch,
+                         [] { return RNNT_STATUS_SUCCESS; });
+}
+
 // mrnnt_forward / mrnnt_hat_forward. hat: the factorised-blank log-softmax (DevProblem::hat) on every route but the
 // chase launch, which has no factorised body: such a call takes the separate log-softmax + recursion.
 RNNTStatus forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
@@ -132,23 +160,15 @@ RNNTStatus backward_impl(const mrnnt_problem *p, const void *ws, const float *gr
     if (!ws) return fail(RNNT_STATUS_INVALID_VALUE, "workspace is null");
     if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
     DevProblem d = make_dev(p, pl, ws);
-    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
-    d.row_state = row_state;
-    d.col_mul = column_order(pl, 2);
     // grad_variant 3 sweeps rows (packed layout only), the others walk lattice columns (the factorised gradient always)
     const int grid = (!hat && tuning().grad_variant == 3 && pl.pad_S1 == 0)
                          ? streaming_grid(pl.N, std::max(1, tuning().grad_grid_per_cu))
-                         : streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    hipError_t e = timed(K_GRAD, stream, [&] {
-        return hat ? launch_hat_grad(d, pl.elem, grad_scale, grads, grid, stream)
-                   : launch_grad(d, pl.elem, grad_scale, grads, grid, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "gradient kernel");
-    if (pl.pad_S1 != 0) {
-        e = launch_pad_zero(d, pl.elem, grads, stream);
-        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
-    }
-    return RNNT_STATUS_SUCCESS;
+                         : 0;
+    return gradient_pass(pl, d, row_state, row_state_len, grads, grid, "gradient kernel", stream,
+                         [&](const DevProblem &dv, int g) {
+                             return hat ? launch_hat_grad(dv, pl.elem, grad_scale, grads, g, stream)
+                                        : launch_grad(dv, pl.elem, grad_scale, grads, g, stream);
+                         });
 }
 
 // mrnnt_align / mrnnt_hat_align
@@ -184,12 +204,7 @@ extern "C" {
 // mrnnt_version, mrnnt_last_error, mrnnt_lattice_bytes / mrnnt_lattice_host: mrnnt_entry.cpp (host-only)
 
 RNNTStatus mrnnt_workspace_size(const mrnnt_problem *p, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    Plan pl;
-    const RNNTStatus st = make_plan(p, &pl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pl.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<Plan>(bytes, [&](Plan *pl) { return make_plan(p, pl); });
 }
 
 RNNTStatus mrnnt_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs_dev, int with_beta,
@@ -280,22 +295,13 @@ struct PathPlan {
 
 // The plan and the host checks of the path entry points, all before any device call.
 RNNTStatus make_path_plan(const mrnnt_problem *p, int num_paths, PathPlan *pp) {
-    if (p && p->alignment)
-        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL: "
-                                               "the band arrays hold the hull of the given paths)");
-    if (num_paths < 1)
-        return fail(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
-    const RNNTStatus st = make_plan(p, &pp->pl, true);
-    if (st != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = pp->pl;
-    if ((int64_t)pl.B * num_paths > 0x7fffffff || pl.B > 65535)
-        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take B <= 65535 and B * num_paths < 2^31");
-    size_t o = pl.total;
-    pp->off_valid = o;
-    o = align_up(o + sizeof(int) * (size_t)pl.B * num_paths);
-    pp->off_carry = o;
-    o = align_up(o + sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
-    pp->total = o;
+    const RNNTStatus st = plan_paths(p && p->alignment, num_paths, pl, [&] { return make_plan(p, &pp->pl, true); });
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    Carver c{pl.total};
+    pp->off_valid = c.take(sizeof(int) * (size_t)pl.B * num_paths);
+    pp->off_carry = c.take(sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
+    pp->total = c.at;
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -347,24 +353,18 @@ RNNTStatus path_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes,
     if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
     if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
-    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
-    d.row_state = row_state;
     PathArgs a = path_args(pp, ws, alignments_dev, num_paths, path_stride);
     a.w = weights_dev;
-    hipError_t e = timed(K_DP, stream, [&] { return launch_path_coef(d, a, pl.T_max, stream); });
-    if (e != hipSuccess) return fail_hip(e, "path coefficient kernel");
-    d.col_mul = column_order(pl, 2);
-    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    e = timed(K_GRAD, stream, [&] {
-        return hat ? launch_hat_path_grad(d, pl.elem, grads, grid, stream)
-                   : launch_path_grad(d, pl.elem, grads, grid, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "path gradient kernel");
-    if (pl.pad_S1 != 0) {
-        e = launch_pad_zero(d, pl.elem, grads, stream);
-        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
-    }
-    return RNNT_STATUS_SUCCESS;
+    return gradient_pass(
+        pl, d, row_state, row_state_len, grads, 0, "path gradient kernel", stream,
+        [&](const DevProblem &dv, int g) {
+            return hat ? launch_hat_path_grad(dv, pl.elem, grads, g, stream)
+                       : launch_path_grad(dv, pl.elem, grads, g, stream);
+        },
+        [&] {
+            const hipError_t e = timed(K_DP, stream, [&] { return launch_path_coef(d, a, pl.T_max, stream); });
+            return e != hipSuccess ? fail_hip(e, "path coefficient kernel") : RNNT_STATUS_SUCCESS;
+        });
 }
 
 }  // namespace
@@ -372,12 +372,7 @@ RNNTStatus path_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes,
 extern "C" {
 
 RNNTStatus mrnnt_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    PathPlan pp;
-    const RNNTStatus st = make_path_plan(p, num_paths, &pp);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pp.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<PathPlan>(bytes, [&](PathPlan *pp) { return make_path_plan(p, num_paths, pp); });
 }
 
 RNNTStatus mrnnt_path_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const int *alignments_dev,
@@ -426,30 +421,17 @@ namespace {
 // mrnnt_expect_*: the loss's plan (a restricting alignment included), then the expectation state A / Bk / R.
 struct ExpectPlan {
     Plan pl;
-    size_t off_A = 0, off_Bk = 0, off_R = 0, total = 0;
+    ExpectState state;
+    size_t total = 0;
 };
 
 RNNTStatus make_expect_plan(const mrnnt_problem *p, ExpectPlan *ep) {
     const RNNTStatus st = make_plan(p, &ep->pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    const Plan &pl = ep->pl;
-    size_t o = pl.total;
-    ep->off_A = o;
-    o = align_up(o + sizeof(double) * (size_t)pl.N);
-    ep->off_Bk = o;
-    o = align_up(o + sizeof(double) * (size_t)pl.N);
-    ep->off_R = o;
-    o = align_up(o + sizeof(double) * (size_t)pl.B);
-    ep->total = o;
+    Carver c{ep->pl.total};
+    ep->state.carve_from(&c, ep->pl);
+    ep->total = c.at;
     return RNNT_STATUS_SUCCESS;
-}
-
-void expect_dev(const ExpectPlan &ep, void *ws, const float *blank_cost_dev, const float *label_cost_dev, DevProblem *d) {
-    d->ex_A = carve<double>(ws, ep.off_A);
-    d->ex_Bk = carve<double>(ws, ep.off_Bk);
-    d->ex_R = carve<double>(ws, ep.off_R);
-    d->ex_wb = blank_cost_dev;
-    d->ex_we = label_cost_dev;
 }
 
 // mrnnt_expect_forward / mrnnt_hat_expect_forward. hat: the forward is mrnnt_hat_forward's (never the chase launch);
@@ -465,7 +447,7 @@ RNNTStatus expect_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes
     // the loss's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
     if ((st = forward_impl(p, ws, ws_bytes, costs_dev, with_grad ? 1 : 0, stream, hat)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, ep.pl, ws);
-    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    ep.state.bind(&d, ws, blank_cost_dev, label_cost_dev);
     const hipError_t e =
         timed(K_DP, stream, [&] { return launch_expect(d, ep.pl.S_max, with_grad ? 1 : 0, expected_dev, stream); });
     if (e != hipSuccess) return fail_hip(e, "expectation recursion kernel");
@@ -485,23 +467,14 @@ RNNTStatus expect_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_byte
     if (!grads) return fail(RNNT_STATUS_INVALID_VALUE, "grads is null");
     if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
     DevProblem d = make_dev(p, pl, ws);
-    if ((st = check_row_state(d, row_state, row_state_len)) != RNNT_STATUS_SUCCESS) return st;
-    d.row_state = row_state;
-    expect_dev(ep, ws, blank_cost_dev, label_cost_dev, &d);
+    ep.state.bind(&d, ws, blank_cost_dev, label_cost_dev);
     d.ex_ge = grad_expected_dev;
     d.ex_gc = grad_costs_dev;
-    d.col_mul = column_order(pl, 2);
-    const int grid = streaming_grid(pl.cols, tuning().grad_grid_per_cu);
-    hipError_t e = timed(K_GRAD, stream, [&] {
-        return hat ? launch_hat_expect_grad(d, pl.elem, grads, grid, stream)
-                   : launch_expect_grad(d, pl.elem, grads, grid, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "expected-cost gradient kernel");
-    if (pl.pad_S1 != 0) {
-        e = launch_pad_zero(d, pl.elem, grads, stream);
-        if (e != hipSuccess) return fail_hip(e, "padding-rows zero kernel");
-    }
-    return RNNT_STATUS_SUCCESS;
+    return gradient_pass(pl, d, row_state, row_state_len, grads, 0, "expected-cost gradient kernel", stream,
+                         [&](const DevProblem &dv, int g) {
+                             return hat ? launch_hat_expect_grad(dv, pl.elem, grads, g, stream)
+                                        : launch_expect_grad(dv, pl.elem, grads, g, stream);
+                         });
 }
 
 }  // namespace
@@ -509,12 +482,7 @@ RNNTStatus expect_backward_impl(const mrnnt_problem *p, void *ws, size_t ws_byte
 extern "C" {
 
 RNNTStatus mrnnt_expect_workspace_size(const mrnnt_problem *p, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    ExpectPlan ep;
-    const RNNTStatus st = make_expect_plan(p, &ep);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = ep.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<ExpectPlan>(bytes, [&](ExpectPlan *ep) { return make_expect_plan(p, ep); });
 }
 
 RNNTStatus mrnnt_expect_forward(const mrnnt_problem *p, void *ws, size_t ws_bytes, const float *blank_cost_dev,

@@ -170,6 +170,16 @@ struct CpuPlan {
 constexpr size_t kAlign = 64;
 size_t align_up(size_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
 
+// carves aligned workspace arrays one after the other; `at` ends as the total
+struct Carver {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t off = at;
+        at = align_up(at + bytes);
+        return off;
+    }
+};
+
 // band: the plan holds the band arrays although the problem has no alignment (mrnnt_cpu_path_*: the paths' hull)
 RNNTStatus make_cpu_plan(const mrnnt_problem *p, CpuPlan *pl, bool band = false) {
     if (!p) return set_error(RNNT_STATUS_INVALID_VALUE, "null problem");
@@ -218,31 +228,47 @@ RNNTStatus make_cpu_plan(const mrnnt_problem *p, CpuPlan *pl, bool band = false)
         return set_error(RNNT_STATUS_INVALID_VALUE, "acts has " + std::to_string(p->num_rows) + " rows but the " +
                                                         (q.pad_S1 ? "padded layout needs " : "lattice needs sum_b T_b(S_b+1) = ") +
                                                         std::to_string(acts_rows));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
-    q.off_den = take(sizeof(float) * q.N);
-    q.off_lpb = take(sizeof(double) * q.N);
-    q.off_lpe = take(sizeof(double) * q.N);
-    q.off_alpha = take(sizeof(double) * q.N);
-    q.off_beta = take(sizeof(double) * q.N);
-    q.off_ll = take(sizeof(double) * q.B);
-    q.off_llb = take(sizeof(double) * q.B);
-    q.off_min = q.align ? take(sizeof(int) * q.cols) : 0;
-    q.off_max = q.align ? take(sizeof(int) * q.cols) : 0;
-    q.total = o;
+    Carver ws;
+    q.off_den = ws.take(sizeof(float) * q.N);
+    q.off_lpb = ws.take(sizeof(double) * q.N);
+    q.off_lpe = ws.take(sizeof(double) * q.N);
+    q.off_alpha = ws.take(sizeof(double) * q.N);
+    q.off_beta = ws.take(sizeof(double) * q.N);
+    q.off_ll = ws.take(sizeof(double) * q.B);
+    q.off_llb = ws.take(sizeof(double) * q.B);
+    q.off_min = q.align ? ws.take(sizeof(int) * q.cols) : 0;
+    q.off_max = q.align ? ws.take(sizeof(int) * q.cols) : 0;
+    q.total = ws.at;
     *pl = std::move(q);
     return RNNT_STATUS_SUCCESS;
+}
+
+// labels of utterance b (null without labels: every S is 0)
+inline const int *utt_labels(const mrnnt_problem *p, int b) {
+    return p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+}
+
+RNNTStatus check_workspace(const void *ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need)
+        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(need) + " bytes");
+    return RNNT_STATUS_SUCCESS;
+}
+
+// the *_workspace_size entry points: the total of the plan that `make` fills
+template <class Plan, class F>
+RNNTStatus plan_bytes(size_t *bytes, F &&make) {
+    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    Plan pl;
+    const RNNTStatus st = make(&pl);
+    if (st == RNNT_STATUS_SUCCESS) *bytes = pl.total;
+    return st;
 }
 
 RNNTStatus check_inputs(const mrnnt_problem *p, const CpuPlan &pl) {
     if (!p->acts) return set_error(RNNT_STATUS_INVALID_VALUE, "acts is null");
     if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
     for (int b = 0; b < pl.B; ++b) {
-        const int *lab = p->labels + (int64_t)b * p->label_stride;
+        const int *lab = utt_labels(p, b);
         for (int s = 0; s < p->S_host[b]; ++s)
             if (lab[s] < 0 || lab[s] >= pl.V)
                 return set_error(RNNT_STATUS_INVALID_VALUE, "label " + std::to_string(lab[s]) + " at (" +
@@ -321,7 +347,7 @@ void build_band(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int n
 // Rows of column (b, t) the recursion can touch: the band max(0, t-(T-S)) <= s <= min(t, S), narrowed under an
 // alignment to the rows alpha(t, [min_s(t), max_s(t)]) and beta(t, [min_s(t-1), max_s(t-1)]) read (the HIP
 // path's align_window, mrnnt_device.h). Every other row only meets -inf state.
-inline void row_window(const CpuPlan &pl, const Views &w, int64_t c, int t, int T, int S, int &lo, int &hi) {
+inline void row_window(const Views &w, int64_t c, int t, int T, int S, int &lo, int &hi) {
     lo = std::max(0, t - (T - S));
     hi = std::min(t, S);
     if (!w.min_s) return;
@@ -369,11 +395,11 @@ void softmax_pass(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int
         const int b = col_utt(pl, c);
         const int t = (int)(c - pl.col_off[b]);
         const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lab = utt_labels(p, b);
         const int64_t r0 = pl.row_off[b] + (int64_t)t * W;  // lattice row of (t, 0)
         const int64_t a0 = acts_row(pl, b, t, W);           // acts row of (t, 0)
         int lo, hi;
-        row_window(pl, w, c, t, T, S, lo, hi);
+        row_window(w, c, t, T, S, lo, hi);
         for (int s = 0; s < W; ++s) {
             const int64_t r = r0 + s;
             if (s < lo || s > hi) {  // finite filler: the recursion only adds it to -inf state
@@ -398,6 +424,17 @@ void softmax_pass(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, int
     }
 }
 
+// band(u): the states before frame u, 0 <= u <= T (the bounds of alpha_utt / beta_utt)
+inline void state_band(const Views &w, int64_t c0, int T, int S, int u, int &lo, int &hi) {
+    lo = std::max(u - (T - S), 0);
+    hi = std::min(u, S);
+    if (w.min_s && u > 0) {
+        lo = std::max(lo, w.min_s[c0 + u - 1]);
+        hi = std::min(hi, w.max_s[c0 + u - 1]);
+    }
+    if (u == 0) hi = 0;
+}
+
 // alpha(t, s) = lse(alpha(t-1, s) + lpb(t, s), alpha(t-1, s-1) + lpe(t, s-1)) on
 // max(min_s(t), t-(T-1-S)) <= s <= min(max_s(t), t+1), -inf elsewhere (cpu_rnnt.h:140-161,
 // cpu_workspace_manager.h:62-64,160-181); returns alpha(T-1, S).
@@ -406,11 +443,8 @@ double alpha_utt(const CpuPlan &pl, const Views &w, int b, int T, int S) {
     const int64_t r0 = pl.row_off[b], c0 = pl.col_off[b];
     double *A = w.alpha + r0;
     for (int t = 0; t < T; ++t) {
-        int lo = std::max(0, t - (T - 1 - S)), hi = std::min(S, t + 1);
-        if (w.min_s) {
-            lo = std::max(lo, w.min_s[c0 + t]);
-            hi = std::min(hi, w.max_s[c0 + t]);
-        }
+        int lo, hi;
+        state_band(w, c0, T, S, t + 1, lo, hi);
         double *a = A + (int64_t)t * W;
         const double *ap = A + (int64_t)(t - 1) * W;
         const double *pb = w.lpb + r0 + (int64_t)t * W;
@@ -436,15 +470,8 @@ double beta_utt(const CpuPlan &pl, const Views &w, int b, int T, int S) {
     const int64_t r0 = pl.row_off[b], c0 = pl.col_off[b];
     double *Bt = w.beta + r0;
     for (int t = T - 1; t >= 0; --t) {
-        int lo = 0, hi = 0;
-        if (t > 0) {
-            lo = std::max(0, t - (T - S));
-            hi = std::min(S, t);
-            if (w.min_s) {
-                lo = std::max(lo, w.min_s[c0 + t - 1]);
-                hi = std::min(hi, w.max_s[c0 + t - 1]);
-            }
-        }
+        int lo, hi;
+        state_band(w, c0, T, S, t, lo, hi);
         double *bt = Bt + (int64_t)t * W;
         const double *bn = Bt + (int64_t)(t + 1) * W;
         const double *pb = w.lpb + r0 + (int64_t)t * W;
@@ -476,11 +503,8 @@ double viterbi_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, in
     double *prev = va.data(), *cur = vb.data();
     prev[0] = 0.0;  // v(-1, s)
     for (int t = 0; t < T; ++t) {
-        int lo = std::max(0, t - (T - 1 - S)), hi = std::min(S, t + 1);
-        if (w.min_s) {
-            lo = std::max(lo, w.min_s[c0 + t]);
-            hi = std::min(hi, w.max_s[c0 + t]);
-        }
+        int lo, hi;
+        state_band(w, c0, T, S, t + 1, lo, hi);
         const double *pb = w.lpb + r0 + (int64_t)t * W;
         const double *pe = w.lpe + r0 + (int64_t)t * W;
         unsigned char *bt = bp + (int64_t)t * W;
@@ -503,7 +527,7 @@ double viterbi_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, in
         std::fill(row, row + out_stride, -1);
         return fin;
     }
-    const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+    const int *lab = utt_labels(p, b);
     int s = S;
     for (int t = T - 1; t >= 0; --t) {
         const int bit = (s > 0 && bp[(int64_t)t * W + s]) ? 1 : 0;
@@ -514,141 +538,204 @@ double viterbi_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, in
     return fin;
 }
 
-// Gradient of one lattice column (b, t), every row s in [0, S] (cpu_rnnt.h:216-249):
+// The label of slot s where row (t, s) has a label arc, else -1: s = S, a label outside [0, V), and a label equal to
+// blank (no such arc) have none.
+inline int slot_label(const int *lab, int s, int S, int V, int blank) {
+    return (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != blank) ? lab[s] : -1;
+}
+
+// Column (b, t) of one utterance: its monotonic band [lo, hi], ll, and the recursion state around the two arcs that
+// leave node (t, s), with the lattice's edge rules in one place: before the first frame alpha is [s == 0], after the
+// last one beta is [s == S] (so [s + 1 == S] behind the label arc), and row s = S has no label arc. Every read stays
+// inside the utterance's own T (S + 1) rows.
+struct ArcState {
+    const double *A, *Bt;  // alpha / beta of the utterance, [T, W]
+    int t, T, S, W, lo, hi;
+    double ll;
+    ArcState(const CpuPlan &pl, const Views &w, int b, int t_, int T_, int S_)
+        : A(w.alpha + pl.row_off[b]), Bt(w.beta + pl.row_off[b]), t(t_), T(T_), S(S_), W(S_ + 1),
+          lo(std::max(0, t_ - (T_ - S_))), hi(std::min(t_, S_)), ll(w.ll[b]) {}
+    bool in_band(int s) const { return s >= lo && s <= hi; }
+    // alpha(t-1, s)
+    double alpha_in(int s) const { return (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s]; }
+    // beta(t, s)
+    double beta_at(int s) const { return Bt[(int64_t)t * W + s]; }
+    // beta(t+1, s): behind the blank arc
+    double beta_blank(int s) const { return (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s]; }
+    // beta(t+1, s+1): behind the label arc
+    double beta_label(int s) const {
+        return (s == S) ? kNegInf : ((t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1]);
+    }
+};
+
+// ---- the dense-gradient pass over row policies (the HIP path's grad_staged_kernel<..., P>, mrnnt_grad.h) -------------
+//
+// grad_pass walks every lattice column (b, t), OpenMP over columns, and every row s in [0, S] of it: the row is either
+// filled with one value without reading acts, or written by the policy's row formula; then the padding rows of the
+// padded layout are zeroed. A row policy P (named after its HIP twin) supplies exactly what differs:
+//   P::Col column(c, b, t, T, S)         what a column sets up once
+//   bool row(col, s, r, a, fill, live)   row s (lattice row r, acts row a): its coefficients, then either false and the
+//                                        value a dead or out-of-band row is filled with, or the row formula on live()
+struct RowsBase {
+    const mrnnt_problem *p;
+    const CpuPlan &pl;
+    const Views &w;
+};
+
+// a live row as grad_pass hands it to the row formula: g[0, V) from z[0, V) (g may be z itself)
+struct RowIO {
+    const float *z;
+    float *g;
+    int l;         // slot_label
+    float zb, zl;  // z[blank], z[l] (0 without a label arc)
+};
+
+template <class P>
+void grad_pass(const P &rows, float *grads, int nt) {
+    const mrnnt_problem *p = rows.p;
+    const CpuPlan &pl = rows.pl;
+    const float *acts = static_cast<const float *>(p->acts);
+    const int V = pl.V, blank = p->blank;
+#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
+    for (int64_t c = 0; c < pl.cols; ++c) {
+        const int b = col_utt(pl, c);
+        const int t = (int)(c - pl.col_off[b]);
+        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
+        const int *lab = utt_labels(p, b);
+        const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
+        const typename P::Col col = rows.column(c, b, t, T, S);
+        for (int s = 0; s < W; ++s) {
+            float *g = grads + (a0 + s) * V;
+            const auto live = [&] {
+                const float *z = acts + (a0 + s) * V;
+                const int l = slot_label(lab, s, S, V, blank);
+                return RowIO{z, g, l, z[blank], l >= 0 ? z[l] : 0.0f};  // read first: grads may alias acts
+            };
+            float fill;
+            if (!rows.row(col, s, r0 + s, a0 + s, fill, live)) std::fill(g, g + V, fill);  // acts not read
+        }
+    }
+    zero_padding_rows(p, pl, grads, V, nt);
+}
+
+// The loss gradient (mrnnt_cpu_backward; cpu_rnnt.h:216-249):
 //   g[v] = e^(z[v] + den + alpha(t-1,s) + beta(t,s) - ll) - [v == blank] e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll)
 //          - [v == label(s), label != blank] e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll),
 // times grad_scale[b]. Out-of-band rows are 0 * scale (NaN * scale for ll = -inf: the reference's exp(... - ll)),
 // in-band rows below the occupancy threshold (kDeadLogOcc) are exact zeros written without reading acts.
-void grad_column(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, const float *scale, float *grads, int b,
-                 int t) {
-    const int T = p->T_host[b], S = p->S_host[b], W = S + 1, V = pl.V, blank = p->blank;
-    const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
-    const float *acts = static_cast<const float *>(p->acts);
-    const float sc = scale ? scale[p->grad_scale_broadcast ? 0 : b] : 1.0f;
-    const double ll = w.ll[b];
-    const float zero = (ll > kNegInf ? 0.0f : std::numeric_limits<float>::quiet_NaN()) * sc;
-    const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
-    const double *A = w.alpha + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
-    const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
-    for (int s = 0; s < W; ++s) {
-        float *g = grads + (a0 + s) * V;
-        if (s < lo || s > hi) {
-            std::fill(g, g + V, zero);
-            continue;
-        }
-        const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s];
-        const double b0 = Bt[(int64_t)t * W + s];
-        const double b1 = (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s];
-        const double b2 = (s == S) ? kNegInf : ((t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1]);
-        const double base = am - ll;
-        if (base + b0 < mrnnt::kDeadLogOcc) {
-            std::fill(g, g + V, 0.0f * sc);
-            continue;
-        }
-        const int64_t r = r0 + s;
-        const float c = (float)((double)w.den[r] + base + b0);
-        const float *z = acts + (a0 + s) * V;
-        const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != blank) ? lab[s] : -1;
-        const float zb = z[blank], zl = l >= 0 ? z[l] : 0.0f;  // read first: grads may alias acts
-        grad_row(z, g, V, c, sc);
-        const float cb = (float)std::exp(w.lpb[r] + base + b1);
-        g[blank] = (vexp(zb + c) - cb) * sc;
-        if (l >= 0) {
-            const float ce = (float)std::exp(w.lpe[r] + base + b2);
-            g[l] = (vexp(zl + c) - ce) * sc;
-        }
+struct LossRows : RowsBase {
+    const float *scale;
+    struct Col : ArcState {
+        float sc, zero;
+    };
+    Col column(int64_t, int b, int t, int T, int S) const {
+        const ArcState band(pl, w, b, t, T, S);
+        const float sc = scale ? scale[p->grad_scale_broadcast ? 0 : b] : 1.0f;
+        return {band, sc, (band.ll > kNegInf ? 0.0f : std::numeric_limits<float>::quiet_NaN()) * sc};
     }
-}
+    template <class Live>
+    bool row(const Col &col, int s, int64_t r, int64_t, float &fill, Live &&live) const {
+        fill = col.zero;
+        if (!col.in_band(s)) return false;
+        const double b0 = col.beta_at(s), base = col.alpha_in(s) - col.ll;
+        fill = 0.0f * col.sc;
+        if (base + b0 < mrnnt::kDeadLogOcc) return false;
+        const float c = (float)((double)w.den[r] + base + b0), sc = col.sc;
+        const RowIO io = live();
+        grad_row(io.z, io.g, pl.V, c, sc);
+        const float cb = (float)std::exp(w.lpb[r] + base + col.beta_blank(s));
+        io.g[p->blank] = (vexp(io.zb + c) - cb) * sc;
+        if (io.l >= 0) {
+            const float ce = (float)std::exp(w.lpe[r] + base + col.beta_label(s));
+            io.g[io.l] = (vexp(io.zl + c) - ce) * sc;
+        }
+        return true;
+    }
+};
 
-// Factorised-blank gradient of one lattice column (mrnnt_cpu_hat_backward; the HIP path's HatRows, mrnnt_hat.hip):
-// with cb / ce the blank / label arc posteriors of the row,
+// The factorised-blank gradient (mrnnt_cpu_hat_backward; the HIP path's HatRows, mrnnt_hat.hip): with cb / ce the
+// blank / label arc posteriors of the row,
 //   g[blank] = ce sigmoid(z_b) - cb sigmoid(-z_b),   g[v != blank] = ce (e^(z_v + den') - [v == label(s)]),
 // times grad_scale[b], each sigmoid from lpb = log sigmoid(z_b) by itself (sigmoid(-z_b) = -expm1(lpb)). A row whose ce
-// and blank element are both zero in fp32 is stored as exact zeros without reading acts; out-of-band rows as
-// grad_column stores them.
-void grad_column_hat(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, const float *scale, float *grads,
-                     int b, int t) {
-    const int T = p->T_host[b], S = p->S_host[b], W = S + 1, V = pl.V, blank = p->blank;
-    const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
-    const float *acts = static_cast<const float *>(p->acts);
-    const float sc = scale ? scale[p->grad_scale_broadcast ? 0 : b] : 1.0f;
-    const double ll = w.ll[b];
-    const float zero = (ll > kNegInf ? 0.0f : std::numeric_limits<float>::quiet_NaN()) * sc;
-    const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
-    const double *A = w.alpha + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
-    const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
-    for (int s = 0; s < W; ++s) {
-        float *g = grads + (a0 + s) * V;
-        if (s < lo || s > hi) {
-            std::fill(g, g + V, zero);
-            continue;
-        }
-        const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s];
-        const double b1 = (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s];
-        const double b2 =
-            (s == S) ? kNegInf : ((t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1]);
-        const double base = am - ll;
-        const int64_t r = r0 + s;
+// and blank element are both zero in fp32 is stored without reading acts, as the out-of-band rows of LossRows are.
+struct HatRows : LossRows {
+    template <class Live>
+    bool row(const Col &col, int s, int64_t r, int64_t, float &fill, Live &&live) const {
+        fill = col.zero;
+        if (!col.in_band(s)) return false;
+        const double base = col.alpha_in(s) - col.ll;
         const double q = w.lpb[r];
-        const double le = w.lpe[r] + base + b2;
-        const float cb = (float)std::exp(q + base + b1);
-        const float ce = s < S ? (float)std::exp(le) : 0.0f;
-        const float gb = (float)((double)ce * std::exp(q) - (double)cb * -std::expm1(q));
-        if (ce == 0.0f && gb == 0.0f) {
-            std::fill(g, g + V, zero);
-            continue;
-        }
-        const float *z = acts + (a0 + s) * V;
-        const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != blank) ? lab[s] : -1;
-        const float zl = l >= 0 ? z[l] : 0.0f;  // read first: grads may alias acts
+        const double le = w.lpe[r] + base + col.beta_label(s);
+        const float cb = (float)std::exp(q + base + col.beta_blank(s));
+        const float ce = s < col.S ? (float)std::exp(le) : 0.0f;
+        // (s = S: no label arc, ce = 0 and its term is absent)
+        const float gb = s < col.S ? (float)((double)ce * std::exp(q) - (double)cb * -std::expm1(q))
+                                       : (float)((double)cb * std::expm1(q));
+        if (ce == 0.0f && gb == 0.0f) return false;
+        const RowIO io = live();
+        const float sc = col.sc;
         if (ce != 0.0f) {  // (ce = 0: no label arc, every non-blank element is 0 -- s = S, or every label masked)
             const float c = (float)((double)w.den[r] + le);
-            grad_row(z, g, V, c, sc);
-            if (l >= 0) g[l] = (vexp(zl + c) - ce) * sc;
+            grad_row(io.z, io.g, pl.V, c, sc);
+            if (io.l >= 0) io.g[io.l] = (vexp(io.zl + c) - ce) * sc;
         } else {
-            std::fill(g, g + V, 0.0f * sc);
+            std::fill(io.g, io.g + pl.V, 0.0f * sc);
         }
-        g[blank] = gb * sc;
+        io.g[p->blank] = gb * sc;
+        return true;
     }
+};
+
+// One row under two signed arc weights, Wb on the blank arc and We on the label arc (mrnnt_cpu_path_backward /
+// mrnnt_cpu_expect_backward; the HIP path's WeightRows::grad, mrnnt_grad.h):
+//   g[v] = (Wb + We) e^(z_v + den) - [v == blank] Wb - [v == label] We.
+inline void weight_row(const RowIO &io, int V, int blank, float den, double, double Wb, double We) {
+    grad_row(io.z, io.g, V, den, (float)(Wb + We));
+    io.g[blank] -= (float)Wb;
+    if (io.l >= 0) io.g[io.l] -= (float)We;
 }
 
-// One factorised-blank row under two signed arc weights (mrnnt_cpu_hat_path_backward / mrnnt_cpu_hat_expect_backward;
-// the HIP path's HatWeightRows, mrnnt_grad.h), in fp64 with the library exp / expm1:
+// The same for a factorised-blank row (mrnnt_cpu_hat_path_backward / mrnnt_cpu_hat_expect_backward; the HIP path's
+// HatWeightRows, mrnnt_grad.h), in fp64 with the library exp / expm1:
 //   g[blank] = We sigmoid(z_b) - Wb sigmoid(-z_b),   g[v != blank] = We (e^(z_v + den') - [v == label]),
 // sigmoid(z_b) = e^lpb and sigmoid(-z_b) = -expm1(lpb), each by itself. den' = +inf (every label masked): no label arc,
-// the non-blank elements are exact zeros. A NaN lpb (z_b NaN or +inf) makes the whole row NaN. g may be z itself.
-void hat_weight_row(const float *z, float *g, int V, int blank, int label, float den, double lpb, double Wb,
-                    double We) {
+// the non-blank elements are exact zeros. A NaN lpb (z_b NaN or +inf) makes the whole row NaN.
+inline void hat_weight_row(const RowIO &io, int V, int blank, float den, double lpb, double Wb, double We) {
     const float gb = (float)(We * std::exp(lpb) - Wb * -std::expm1(lpb));
     if (den == std::numeric_limits<float>::infinity() && lpb == lpb) {
-        std::fill(g, g + V, 0.0f);
+        std::fill(io.g, io.g + V, 0.0f);
     } else {
         const double d = lpb == lpb ? (double)den : lpb;
-        for (int v = 0; v < V; ++v) g[v] = (float)(We * (std::exp((double)z[v] + d) - (v == label ? 1.0 : 0.0)));
+        for (int v = 0; v < V; ++v)
+            io.g[v] = (float)(We * (std::exp((double)io.z[v] + d) - (v == io.l ? 1.0 : 0.0)));
     }
-    g[blank] = gb;
+    io.g[blank] = gb;
 }
 
+// A weight policy P (column; weights: the two arc weights of a row, false: both zero) under the row formula F
+template <class P, auto F>
+struct WeightedRows : P {
+    template <class Live>
+    bool row(const typename P::Col &col, int s, int64_t r, int64_t a, float &fill, Live &&live) const {
+        double Wb, We;
+        if (!this->weights(col, s, r, a, Wb, We, fill)) return false;
+        F(live(), this->pl.V, this->p->blank, this->w.den[r], this->w.lpb[r], Wb, We);
+        return true;
+    }
+};
+
 // Arc posteriors of row (t, s) inside the monotonic band (mrnnt_cpu_posteriors; the HIP path's row_post,
-// mrnnt_posterior.hip): the blank and label corrections of grad_column in fp64,
+// mrnnt_posterior.hip): the blank and label corrections of LossRows in fp64,
 //   bp = e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll),  ep = e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll)  (0 at s = S).
 // An unreachable row (alpha(t-1,s) or beta(t,s) = -inf) is exactly 0, decided before lp is read.
-inline void row_posteriors(const CpuPlan &pl, const Views &w, int b, int t, int T, int S, int s, double ll, double *bp,
-                           double *ep) {
-    const int W = S + 1;
-    const double *A = w.alpha + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
+inline void row_posteriors(const CpuPlan &pl, const Views &w, int b, const ArcState &col, int s, double *bp, double *ep) {
     *bp = *ep = 0.0;
-    const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : A[(int64_t)(t - 1) * W + s];
-    const double b0 = Bt[(int64_t)t * W + s];
-    if (am == kNegInf || b0 == kNegInf) return;
-    const int64_t r = pl.row_off[b] + (int64_t)t * W + s;
-    const double base = am - ll;
-    const double b1 = (t == T - 1) ? (s == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s];
-    *bp = std::exp(w.lpb[r] + base + b1);
-    if (s < S) {
-        const double b2 = (t == T - 1) ? (s + 1 == S ? 0.0 : kNegInf) : Bt[(int64_t)(t + 1) * W + s + 1];
-        *ep = std::exp(w.lpe[r] + base + b2);
-    }
+    const double am = col.alpha_in(s);
+    if (am == kNegInf || col.beta_at(s) == kNegInf) return;
+    const int64_t r = pl.row_off[b] + (int64_t)col.t * col.W + s;
+    const double base = am - col.ll;
+    *bp = std::exp(w.lpb[r] + base + col.beta_blank(s));
+    if (s < col.S) *ep = std::exp(w.lpe[r] + base + col.beta_label(s));
 }
 
 }  // namespace
@@ -659,12 +746,7 @@ inline void row_posteriors(const CpuPlan &pl, const Views &w, int b, int t, int 
 extern "C" {
 
 RNNTStatus mrnnt_cpu_workspace_size(const mrnnt_problem *p, size_t *bytes) {
-    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    CpuPlan pl;
-    const RNNTStatus st = make_cpu_plan(p, &pl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pl.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_bytes<CpuPlan>(bytes, [&](CpuPlan *pl) { return make_cpu_plan(p, pl); });
 }
 
 static RNNTStatus cpu_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_bytes, float *costs, int with_beta,
@@ -673,8 +755,7 @@ static RNNTStatus cpu_forward_impl(const mrnnt_problem *p, void *ws, size_t ws_b
     RNNTStatus st = make_cpu_plan(p, &pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_inputs(p, pl)) != RNNT_STATUS_SUCCESS) return st;
-    if (!ws || ws_bytes < pl.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pl.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, pl.total)) != RNNT_STATUS_SUCCESS) return st;
     const Views w = views(pl, ws);
     const int nt = threads_of(num_threads);
     if (pl.align) build_band(p, pl, w, nt);
@@ -715,8 +796,7 @@ static RNNTStatus cpu_align_impl(const mrnnt_problem *p, void *ws, size_t ws_byt
         return set_error(RNNT_STATUS_INVALID_VALUE, "alignment_out row stride " + std::to_string(out_stride) +
                                                         " < max input length " + std::to_string(pl.T_max));
     if ((st = check_inputs(p, pl)) != RNNT_STATUS_SUCCESS) return st;
-    if (!ws || ws_bytes < pl.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pl.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, pl.total)) != RNNT_STATUS_SUCCESS) return st;
     const Views w = views(pl, ws);
     const int nt = threads_of(num_threads);
     // p->alignment may be alignment_out itself: the band is built from it before any row is written
@@ -750,13 +830,8 @@ static RNNTStatus cpu_backward_impl(const mrnnt_problem *p, const void *ws, cons
     if (!grads) return set_error(RNNT_STATUS_INVALID_VALUE, "grads is null");
     const Views w = views(pl, const_cast<void *>(ws));
     const int nt = threads_of(num_threads);
-#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
-    for (int64_t c = 0; c < pl.cols; ++c) {
-        const int b = col_utt(pl, c);
-        if (hat) grad_column_hat(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
-        else grad_column(p, pl, w, grad_scale, grads, b, (int)(c - pl.col_off[b]));
-    }
-    zero_padding_rows(p, pl, grads, pl.V, nt);
+    if (hat) grad_pass(HatRows{{{p, pl, w}, grad_scale}}, grads, nt);
+    else grad_pass(LossRows{{p, pl, w}, grad_scale}, grads, nt);
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -791,14 +866,13 @@ RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *b
             const int b = col_utt(pl, c);
             const int t = (int)(c - pl.col_off[b]);
             const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
-            const double ll = w.ll[b];
-            const bool fin = std::isfinite(ll);
-            const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
+            const ArcState col(pl, w, b, t, T, S);
+            const bool fin = std::isfinite(col.ll);
             const int64_t a0 = acts_row(pl, b, t, W);
             double sum = 0.0;
             for (int s = 0; s < W; ++s) {
                 double bp = 0.0, ep = 0.0;
-                if (fin && s >= lo && s <= hi) row_posteriors(pl, w, b, t, T, S, s, ll, &bp, &ep);
+                if (fin && col.in_band(s)) row_posteriors(pl, w, b, col, s, &bp, &ep);
                 if (blank_post) blank_post[a0 + s] = fin ? (float)bp : nan;
                 if (label_post) label_post[a0 + s] = fin ? (float)ep : nan;
                 sum += ep;
@@ -818,14 +892,13 @@ RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *b
             const int b = (int)(std::upper_bound(lab_off.begin(), lab_off.end(), i) - lab_off.begin()) - 1;
             const int s = (int)(i - lab_off[b]);
             const int T = p->T_host[b], S = p->S_host[b];
-            const double ll = w.ll[b];
             double sum = 0.0;
             for (int t = s; t <= s + (T - S); ++t) {  // the frames with (t, s) inside the band
                 double bp, ep;
-                row_posteriors(pl, w, b, t, T, S, s, ll, &bp, &ep);
+                row_posteriors(pl, w, b, ArcState(pl, w, b, t, T, S), s, &bp, &ep);
                 sum += (double)t * ep;
             }
-            label_time[(int64_t)b * time_stride + s] = std::isfinite(ll) ? (float)sum : nan;
+            label_time[(int64_t)b * time_stride + s] = std::isfinite(w.ll[b]) ? (float)sum : nan;
         }
         for (int b = 0; b < pl.B; ++b)
             std::fill(label_time + (int64_t)b * time_stride + p->S_host[b], label_time + (int64_t)(b + 1) * time_stride,
@@ -868,19 +941,19 @@ RNNTStatus mrnnt_cpu_sample(const mrnnt_problem *p, const void *ws, int num_samp
             if (path_costs) path_costs[i] = ll == kNegInf ? std::numeric_limits<float>::infinity() : nan;
             continue;
         }
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lab = utt_labels(p, b);
         const uint32_t smp = (uint32_t)(first_sample + i % num_samples);
-        const double *pb = w.lpb + pl.row_off[b], *pe = w.lpe + pl.row_off[b], *Bt = w.beta + pl.row_off[b];
+        const double *pb = w.lpb + pl.row_off[b], *pe = w.lpe + pl.row_off[b];
         uint32_t word[4] = {0, 0, 0, 0};
         int s = 0;
         double cost = 0.0;
         for (int t = 0; t < T; ++t) {
             if ((t & 3) == 0) mrnnt::sample_block(seed, (uint32_t)(t >> 2), smp, (uint32_t)b, word);
             const int64_t r = (int64_t)t * W + s;
-            const bool last = t == T - 1;
+            const ArcState arc(pl, w, b, t, T, S);
             double x = kNegInf, y = kNegInf;
-            if (T - 1 - t >= S - s) x = pb[r] + (last ? 0.0 : Bt[r + W]);  // else the blank arc leaves the band
-            if (s < S) y = pe[r] + (last ? (s + 1 == S ? 0.0 : kNegInf) : Bt[r + W + 1]);
+            if (T - 1 - t >= S - s) x = pb[r] + arc.beta_blank(s);  // else the blank arc leaves the band
+            if (s < S) y = pe[r] + arc.beta_label(s);
             const bool take = mrnnt::sample_uniform(word[t & 3]) < mrnnt::sample_p_label(x, y) && s < S;
             cost += take ? pe[r] : pb[r];
             row[t] = take ? lab[s] : p->blank;
@@ -914,8 +987,9 @@ RNNTStatus make_cpu_path_plan(const mrnnt_problem *p, int num_paths, const int *
         return set_error(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
     const RNNTStatus st = make_cpu_plan(p, &pp->pl, true);
     if (st != RNNT_STATUS_SUCCESS) return st;
-    pp->off_valid = pp->pl.total;
-    pp->total = align_up(pp->off_valid + sizeof(int) * (size_t)pp->pl.B * num_paths);
+    Carver ws{pp->pl.total};
+    pp->off_valid = ws.take(sizeof(int) * (size_t)pp->pl.B * num_paths);
+    pp->total = ws.at;
     if (sizing) return RNNT_STATUS_SUCCESS;
     if (!alignments) return set_error(RNNT_STATUS_INVALID_VALUE, "alignments is null");
     if (path_stride < pp->pl.T_max)
@@ -943,17 +1017,32 @@ inline bool walk_path(const int *row, const int *lab, int T, int S, int blank, F
     return s == S;
 }
 
+// The path-score gradient (mrnnt_cpu_path_backward; the HIP path's PathRows / HatPathRows, mrnnt_path.hip): the arc
+// weights are the sums the caller left in w.alpha (Wb) / w.beta (We) over the hull rows; a row outside the hull, or
+// with both weights zero, is exact zeros.
+struct PathWeights : RowsBase {
+    struct Col {
+        int lo, hi;
+    };
+    Col column(int64_t c, int, int, int, int S) const { return {w.min_s[c] - 1, std::min(w.max_s[c], S)}; }
+    bool weights(const Col &col, int s, int64_t r, int64_t, double &Wb, double &We, float &fill) const {
+        const bool in = s >= col.lo && s <= col.hi;
+        Wb = in ? w.alpha[r] : 0.0;
+        We = in ? w.beta[r] : 0.0;
+        fill = 0.0f;
+        return Wb != 0.0 || We != 0.0;
+    }
+};
+using PathRows = WeightedRows<PathWeights, weight_row>;
+using HatPathRows = WeightedRows<PathWeights, hat_weight_row>;
+
 }  // namespace
 
 extern "C" {
 
 RNNTStatus mrnnt_cpu_path_workspace_size(const mrnnt_problem *p, int num_paths, size_t *bytes) {
-    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    CpuPathPlan pp;
-    const RNNTStatus st = make_cpu_path_plan(p, num_paths, nullptr, 0, true, &pp);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pp.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_bytes<CpuPathPlan>(
+        bytes, [&](CpuPathPlan *pp) { return make_cpu_path_plan(p, num_paths, nullptr, 0, true, pp); });
 }
 
 // mrnnt_cpu_path_forward / mrnnt_cpu_hat_path_forward
@@ -965,8 +1054,7 @@ static RNNTStatus cpu_path_forward_impl(const mrnnt_problem *p, void *ws, size_t
     if (st != RNNT_STATUS_SUCCESS) return st;
     const CpuPlan &pl = pp.pl;
     if ((st = check_inputs(p, pl)) != RNNT_STATUS_SUCCESS) return st;
-    if (!ws || ws_bytes < pp.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pp.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     const Views w = views(pl, ws);
     int *valid = reinterpret_cast<int *>(static_cast<char *>(ws) + pp.off_valid);
     const int nt = threads_of(num_threads);
@@ -976,7 +1064,7 @@ static RNNTStatus cpu_path_forward_impl(const mrnnt_problem *p, void *ws, size_t
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
     for (int b = 0; b < pl.B; ++b) {
         const int T = p->T_host[b], S = p->S_host[b];
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lab = utt_labels(p, b);
         int *lo = w.min_s + pl.col_off[b], *hi = w.max_s + pl.col_off[b];
         std::fill(lo, lo + T, kHullEmpty - 1);
         std::fill(hi, hi + T, -1);
@@ -1002,7 +1090,7 @@ static RNNTStatus cpu_path_forward_impl(const mrnnt_problem *p, void *ws, size_t
             continue;
         }
         const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lab = utt_labels(p, b);
         const double *pb = w.lpb + pl.row_off[b], *pe = w.lpe + pl.row_off[b];
         double sum = 0.0;
         walk_path(alignments + i * path_stride, lab, T, S, p->blank, [&](int t, int s, bool label) {
@@ -1035,17 +1123,16 @@ static RNNTStatus cpu_path_backward_impl(const mrnnt_problem *p, void *ws, size_
     if (!p->acts) return set_error(RNNT_STATUS_INVALID_VALUE, "acts is null");
     if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
     if (!grads) return set_error(RNNT_STATUS_INVALID_VALUE, "grads is null");
-    if (!ws || ws_bytes < pp.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(pp.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, pp.total)) != RNNT_STATUS_SUCCESS) return st;
     const Views w = views(pl, ws);
     const int *valid = reinterpret_cast<const int *>(static_cast<const char *>(ws) + pp.off_valid);
     const int nt = threads_of(num_threads);
-    const int K = num_paths, V = pl.V;
+    const int K = num_paths;
     // Wb (w.alpha) / We (w.beta): zero over the hull rows, then the valid paths' weights in ascending k
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
     for (int b = 0; b < pl.B; ++b) {
         const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
+        const int *lab = utt_labels(p, b);
         const int *lo = w.min_s + pl.col_off[b], *hi = w.max_s + pl.col_off[b];
         double *wb = w.alpha + pl.row_off[b], *we = w.beta + pl.row_off[b];
         for (int t = 0; t < T; ++t)
@@ -1059,33 +1146,8 @@ static RNNTStatus cpu_path_backward_impl(const mrnnt_problem *p, void *ws, size_
             });
         }
     }
-    const float *acts = static_cast<const float *>(p->acts);
-#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
-    for (int64_t c = 0; c < pl.cols; ++c) {
-        const int b = col_utt(pl, c);
-        const int t = (int)(c - pl.col_off[b]);
-        const int S = p->S_host[b], W = S + 1;
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
-        const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
-        const int lo = w.min_s[c] - 1, hi = std::min(w.max_s[c], S);
-        for (int s = 0; s < W; ++s) {
-            float *g = grads + (a0 + s) * V;
-            const double wb = (s >= lo && s <= hi) ? w.alpha[r0 + s] : 0.0, we = (s >= lo && s <= hi) ? w.beta[r0 + s] : 0.0;
-            if (!(wb != 0.0 || we != 0.0)) {  // exact zeros, acts not read
-                std::fill(g, g + V, 0.0f);
-                continue;
-            }
-            if (hat) {
-                const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != p->blank) ? lab[s] : -1;
-                hat_weight_row(acts + (a0 + s) * V, g, V, p->blank, l, w.den[r0 + s], w.lpb[r0 + s], wb, we);
-                continue;
-            }
-            grad_row(acts + (a0 + s) * V, g, V, w.den[r0 + s], (float)(wb + we));
-            g[p->blank] -= (float)wb;
-            if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)we;
-        }
-    }
-    zero_padding_rows(p, pl, grads, V, nt);
+    if (hat) grad_pass(HatPathRows{{{p, pl, w}}}, grads, nt);
+    else grad_pass(PathRows{{{p, pl, w}}}, grads, nt);
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -1122,29 +1184,20 @@ namespace {
 
 struct CpuExpectPlan {
     CpuPlan pl;
-    size_t off_A = 0, off_Bk = 0, off_R = 0, total = 0;
+    size_t off_A = 0, off_Bk = 0, off_R = 0, total = 0;  // the cost states A / Bk [N], the expectations R [B]
+    static double *view(void *ws, size_t off) { return reinterpret_cast<double *>(static_cast<char *>(ws) + off); }
 };
 
 RNNTStatus make_cpu_expect_plan(const mrnnt_problem *p, CpuExpectPlan *ep) {
     const RNNTStatus st = make_cpu_plan(p, &ep->pl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const CpuPlan &pl = ep->pl;
-    ep->off_A = pl.total;
-    ep->off_Bk = align_up(ep->off_A + sizeof(double) * (size_t)pl.N);
-    ep->off_R = align_up(ep->off_Bk + sizeof(double) * (size_t)pl.N);
-    ep->total = align_up(ep->off_R + sizeof(double) * (size_t)pl.B);
+    Carver ws{pl.total};
+    ep->off_A = ws.take(sizeof(double) * (size_t)pl.N);
+    ep->off_Bk = ws.take(sizeof(double) * (size_t)pl.N);
+    ep->off_R = ws.take(sizeof(double) * (size_t)pl.B);
+    ep->total = ws.at;
     return RNNT_STATUS_SUCCESS;
-}
-
-// band(u): the states before frame u, 0 <= u <= T (the bounds of alpha_utt / beta_utt)
-inline void state_band(const Views &w, int64_t c0, int T, int S, int u, int &lo, int &hi) {
-    lo = std::max(u - (T - S), 0);
-    hi = std::min(u, S);
-    if (w.min_s && u > 0) {
-        lo = std::max(lo, w.min_s[c0 + u - 1]);
-        hi = std::min(hi, w.max_s[c0 + u - 1]);
-    }
-    if (u == 0) hi = 0;
 }
 
 // new = q * self + p * neighbour + c: the convex mix of the blank arc (log-weight x, cost cx) and the label arc (y, cy);
@@ -1200,17 +1253,53 @@ double expect_utt(const mrnnt_problem *p, const CpuPlan &pl, const Views &w, dou
     return bwd ? O[0] : O[(int64_t)(T - 1) * W + S];
 }
 
+// The expected-cost gradient (mrnnt_cpu_expect_backward; the HIP path's ExpectRows / HatExpectRows, mrnnt_expect.hip):
+// with pb / pe the arc posteriors of the row and A / Bk the cost states before and behind the arc,
+//   W = posterior * (grad_costs - grad_expected * (A(t-1, s) + arc cost + Bk behind the arc - R))
+// per arc. A row outside the band, below the occupancy threshold, or with both weights zero in fp32 is exact zeros
+// (NaN without a finite ll).
+struct ExpectWeights : RowsBase {
+    const float *blank_cost, *label_cost, *grad_expected, *grad_costs;
+    const double *A, *Bk, *Rv;
+    struct Col : ArcState {
+        double R, ge, gc;
+        bool fin, last;
+    };
+    Col column(int64_t, int b, int t, int T, int S) const {
+        const ArcState band(pl, w, b, t, T, S);
+        return {band, Rv[b], grad_expected ? (double)grad_expected[b] : 0.0, grad_costs ? (double)grad_costs[b] : 0.0,
+                std::isfinite(band.ll), t == T - 1};
+    }
+    bool weights(const Col &col, int s, int64_t r, int64_t a, double &Wb, double &We, float &fill) const {
+        const int t = col.t, W = col.W;
+        Wb = We = 0.0;
+        if (col.fin && col.in_band(s)) {
+            const double bs = col.alpha_in(s) - col.ll;
+            if (!(bs + col.beta_at(s) < mrnnt::kDeadLogOcc)) {
+                const double pb = std::exp(w.lpb[r] + bs + col.beta_blank(s));
+                const double pe = (s < col.S) ? std::exp(w.lpe[r] + bs + col.beta_label(s)) : 0.0;
+                const double ap = (t == 0) ? 0.0 : A[r - W];
+                if (pb != 0.0)
+                    Wb = pb * (col.gc - col.ge * (ap + (blank_cost ? (double)blank_cost[a] : 0.0) +
+                                                  (col.last ? 0.0 : Bk[r + W]) - col.R));
+                if (pe != 0.0)
+                    We = pe * (col.gc - col.ge * (ap + (label_cost ? (double)label_cost[a] : 0.0) +
+                                                  (col.last ? 0.0 : Bk[r + W + 1]) - col.R));
+            }
+        }
+        fill = col.fin ? 0.0f : std::numeric_limits<float>::quiet_NaN();
+        return !((float)Wb == 0.0f && (float)We == 0.0f);
+    }
+};
+using ExpectRows = WeightedRows<ExpectWeights, weight_row>;
+using HatExpectRows = WeightedRows<ExpectWeights, hat_weight_row>;
+
 }  // namespace
 
 extern "C" {
 
 RNNTStatus mrnnt_cpu_expect_workspace_size(const mrnnt_problem *p, size_t *bytes) {
-    if (!bytes) return set_error(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    CpuExpectPlan ep;
-    const RNNTStatus st = make_cpu_expect_plan(p, &ep);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = ep.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_bytes<CpuExpectPlan>(bytes, [&](CpuExpectPlan *ep) { return make_cpu_expect_plan(p, ep); });
 }
 
 // mrnnt_cpu_expect_forward / mrnnt_cpu_hat_expect_forward
@@ -1221,14 +1310,11 @@ static RNNTStatus cpu_expect_forward_impl(const mrnnt_problem *p, void *ws, size
     RNNTStatus st = make_cpu_expect_plan(p, &ep);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const CpuPlan &pl = ep.pl;
-    if (!ws || ws_bytes < ep.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(ep.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = cpu_forward_impl(p, ws, ws_bytes, costs, with_grad ? 1 : 0, num_threads, hat)) != RNNT_STATUS_SUCCESS)
         return st;
     const Views w = views(pl, ws);
-    char *base = static_cast<char *>(ws);
-    double *A = reinterpret_cast<double *>(base + ep.off_A), *Bk = reinterpret_cast<double *>(base + ep.off_Bk);
-    double *R = reinterpret_cast<double *>(base + ep.off_R);
+    double *A = ep.view(ws, ep.off_A), *Bk = ep.view(ws, ep.off_Bk), *R = ep.view(ws, ep.off_R);
     const int nt = threads_of(num_threads);
     const int dirs = with_grad ? 2 : 1;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
@@ -1269,61 +1355,13 @@ static RNNTStatus cpu_expect_backward_impl(const mrnnt_problem *p, void *ws, siz
     if (!p->acts) return set_error(RNNT_STATUS_INVALID_VALUE, "acts is null");
     if (pl.S_max > 0 && !p->labels) return set_error(RNNT_STATUS_INVALID_VALUE, "labels is null");
     if (!grads) return set_error(RNNT_STATUS_INVALID_VALUE, "grads is null");
-    if (!ws || ws_bytes < ep.total)
-        return set_error(RNNT_STATUS_INVALID_VALUE, "workspace too small: need " + std::to_string(ep.total) + " bytes");
+    if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
     const Views w = views(pl, ws);
-    const char *base = static_cast<const char *>(ws);
-    const double *A = reinterpret_cast<const double *>(base + ep.off_A);
-    const double *Bk = reinterpret_cast<const double *>(base + ep.off_Bk);
-    const double *Rv = reinterpret_cast<const double *>(base + ep.off_R);
     const int nt = threads_of(num_threads);
-    const int V = pl.V;
-    const float *acts = static_cast<const float *>(p->acts);
-#pragma omp parallel for schedule(dynamic, 4) num_threads(nt)
-    for (int64_t c = 0; c < pl.cols; ++c) {
-        const int b = col_utt(pl, c);
-        const int t = (int)(c - pl.col_off[b]);
-        const int T = p->T_host[b], S = p->S_host[b], W = S + 1;
-        const int *lab = p->labels ? p->labels + (int64_t)b * p->label_stride : nullptr;
-        const int64_t r0 = pl.row_off[b] + (int64_t)t * W, a0 = acts_row(pl, b, t, W);
-        const double ll = w.ll[b], R = Rv[b];
-        const bool fin = std::isfinite(ll), last = t == T - 1;
-        const double ge = grad_expected ? (double)grad_expected[b] : 0.0, gc = grad_costs ? (double)grad_costs[b] : 0.0;
-        const int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
-        for (int s = 0; s < W; ++s) {
-            float *g = grads + (a0 + s) * V;
-            const int64_t r = r0 + s;
-            double Wb = 0.0, We = 0.0;
-            if (fin && s >= lo && s <= hi) {
-                const double am = (t == 0) ? (s == 0 ? 0.0 : kNegInf) : w.alpha[r - W];
-                const double bs = am - ll;
-                if (!(bs + w.beta[r] < mrnnt::kDeadLogOcc)) {
-                    const double b1 = last ? (s == S ? 0.0 : kNegInf) : w.beta[r + W];
-                    const double b2 = (s == S) ? kNegInf : (last ? (s + 1 == S ? 0.0 : kNegInf) : w.beta[r + W + 1]);
-                    const double pb = std::exp(w.lpb[r] + bs + b1), pe = (s < S) ? std::exp(w.lpe[r] + bs + b2) : 0.0;
-                    const double ap = (t == 0) ? 0.0 : A[r - W];
-                    if (pb != 0.0)
-                        Wb = pb * (gc - ge * (ap + (blank_cost ? (double)blank_cost[a0 + s] : 0.0) + (last ? 0.0 : Bk[r + W]) - R));
-                    if (pe != 0.0)
-                        We = pe * (gc - ge * (ap + (label_cost ? (double)label_cost[a0 + s] : 0.0) +
-                                              (last ? 0.0 : Bk[r + W + 1]) - R));
-                }
-            }
-            if ((float)Wb == 0.0f && (float)We == 0.0f) {  // exact zeros (NaN: no finite ll), acts not read
-                std::fill(g, g + V, fin ? 0.0f : std::numeric_limits<float>::quiet_NaN());
-                continue;
-            }
-            if (hat) {
-                const int l = (s < S && (unsigned)lab[s] < (unsigned)V && lab[s] != p->blank) ? lab[s] : -1;
-                hat_weight_row(acts + (a0 + s) * V, g, V, p->blank, l, w.den[r], w.lpb[r], Wb, We);
-                continue;
-            }
-            grad_row(acts + (a0 + s) * V, g, V, w.den[r], (float)(Wb + We));
-            g[p->blank] -= (float)Wb;
-            if (s < S && lab[s] != p->blank) g[lab[s]] -= (float)We;
-        }
-    }
-    zero_padding_rows(p, pl, grads, V, nt);
+    const ExpectWeights x{{p, pl, w}, blank_cost, label_cost, grad_expected, grad_costs,
+                          ep.view(ws, ep.off_A), ep.view(ws, ep.off_Bk), ep.view(ws, ep.off_R)};
+    if (hat) grad_pass(HatExpectRows{x}, grads, nt);
+    else grad_pass(ExpectRows{x}, grads, nt);
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -1530,14 +1568,13 @@ float &CpuRNNTWorkspaceManager<float>::get_denom(int b, int t, int s) {
     const int T = st_->T[b], S = st_->S[b];
     const int64_t c = st_->col_off[b] + t, r = st_->row_off[b] + (int64_t)t * (S + 1) + s;
     // rows the last computation reduced: the band (and alignment window), as in softmax_pass / row_window
-    int lo = std::max(0, t - (T - S)), hi = std::min(t, S);
+    Views band{};
     if (st_->computed_restricted && !st_->cmin_s.empty()) {
-        int wlo = st_->cmin_s[c] - 1, whi = st_->cmax_s[c];
-        wlo = std::min(wlo, t > 0 ? st_->cmin_s[c - 1] : 0);
-        whi = std::max(whi, t > 0 ? st_->cmax_s[c - 1] : 0);
-        lo = std::max(lo, wlo);
-        hi = std::min(hi, whi);
+        band.min_s = st_->cmin_s.data();
+        band.max_s = st_->cmax_s.data();
     }
+    int lo, hi;
+    row_window(band, c, t, T, S, lo, hi);
     if (s < lo || s > hi) {  // never read by the computation: reduce it now (the reference's pass covers every row)
         float m;
         double sum;

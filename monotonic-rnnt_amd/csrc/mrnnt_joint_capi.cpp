@@ -72,25 +72,17 @@ RNNTStatus make_joint_plan(const mrnnt_joint_problem *jp, JointPlan *jl) {
         return fail(RNNT_STATUS_INVALID_VALUE, "hact_ld must be 0 or a multiple of 8 that is >= H");
     if (jp->enc_stride < (int64_t)q.base.T_max * H || jp->pred_stride < (int64_t)(q.base.S_max + 1) * H)
         return fail(RNNT_STATUS_INVALID_VALUE, "enc/pred utterance strides smaller than max T * H / (max S + 1) * H");
-    for (int b = 0; b < jp->B; ++b) {
-        const int T = jp->T_host[b], S = jp->S_host[b];
-        for (int t = 0; t < T; ++t) q.n_inband += std::min(t, S) - std::max(0, t - (T - S)) + 1;
-    }
-    size_t o = q.base.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
+    for (int b = 0; b < jp->B; ++b) q.n_inband += inband_rows(jp->T_host[b], jp->S_host[b]);
+    Carver c{q.base.total};
     // per-column counts + their exclusive scan, and the scan's tile sums (launch_row_list)
-    q.off_cnt = take(sizeof(int64_t) * (q.base.cols + 2 + (q.base.cols + 1023) / 1024));
-    q.off_lcol = take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
-    q.off_ls = take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
-    q.off_total = take(sizeof(unsigned long long));
-    q.off_wplain = take(sizeof(int));  // the forward's weight-bound flag (launch_joint_wbound)
+    q.off_cnt = c.take(sizeof(int64_t) * (q.base.cols + 2 + (q.base.cols + 1023) / 1024));
+    q.off_lcol = c.take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
+    q.off_ls = c.take(sizeof(int) * std::max<int64_t>(1, q.n_inband));
+    q.off_total = c.take(sizeof(unsigned long long));
+    q.off_wplain = c.take(sizeof(int));  // the forward's weight-bound flag (launch_joint_wbound)
     // the gradient pass's per-workgroup dbias column sums (fixed-order reduction), when there is a bias
-    q.off_dbias = (jp->bias && H <= 512) ? take(joint_dbias_part_bytes(std::max<int64_t>(1, q.n_inband), jp->V)) : 0;
-    q.total = o;
+    q.off_dbias = (jp->bias && H <= 512) ? c.take(joint_dbias_part_bytes(std::max<int64_t>(1, q.n_inband), jp->V)) : 0;
+    q.total = c.at;
     *jl = q;
     return RNNT_STATUS_SUCCESS;
 }
@@ -122,6 +114,27 @@ JointArgs joint_args(const mrnnt_joint_problem *jp, const JointPlan &jl, void *w
     return j;
 }
 
+// The joint forward pass over the rows d's band lets through (the row list in mode 0): lpb / lpe and den of each into
+// the workspace. windowed: the band is narrower than the monotonic one, the number of rows stays on the device.
+RNNTStatus joint_forward_pass(const mrnnt_joint_problem *jp, const JointPlan &jl, void *ws, const DevProblem &d,
+                              bool windowed, hipStream_t stream) {
+    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
+    hipError_t e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol),
+                                   carve<int>(ws, jl.off_ls), total, stream);
+    if (e != hipSuccess) return fail_hip(e, "row list kernels");
+    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
+    if (windowed) j.n_dev = total;
+    // the weight bound decides the forward's epilogue on the device (no host sync): counted in the forward's time
+    int *wplain = carve<int>(ws, jl.off_wplain);
+    j.wplain = wplain;
+    e = timed(K_JOINT_FWD, stream, [&] {
+        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
+        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
+    });
+    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    return RNNT_STATUS_SUCCESS;
+}
+
 // What mrnnt_joint_forward and mrnnt_joint_align share after the plan: pointer and workspace checks, the lattice (and
 // the alignment band), then the joint log-softmax pass that leaves lpb / lpe of every row the recursion can use in the
 // workspace. *out: the device problem for the launch that follows (launch_dp / launch_viterbi). hat: the
@@ -141,20 +154,7 @@ RNNTStatus joint_log_softmax(const mrnnt_joint_problem *jp, const JointPlan &jl,
     // out-of-band lp entries must be finite for the recursion (the acts path zero-fills them in its pass)
     hipError_t e = launch_zero(carve<char>(ws, pl.off_lp), pl.off_alpha - pl.off_lp, stream);
     if (e != hipSuccess) return fail_hip(e, "lp zero fill");
-    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
-    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
-                        total, stream);
-    if (e != hipSuccess) return fail_hip(e, "row list kernels");
-    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
-    if (pl.align) j.n_dev = total;  // alignment windows
-    // the weight bound decides the forward's epilogue on the device (no host sync): counted in the forward's time
-    int *wplain = carve<int>(ws, jl.off_wplain);
-    j.wplain = wplain;
-    e = timed(K_JOINT_FWD, stream, [&] {
-        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
-        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    if ((st = joint_forward_pass(jp, jl, ws, d, pl.align, stream)) != RNNT_STATUS_SUCCESS) return st;  // alignment windows
     *out = d;
     return RNNT_STATUS_SUCCESS;
 }
@@ -170,34 +170,19 @@ struct JointPathPlan {
 
 // The plan and the host checks of the joint path entry points, all before any device call (make_path_plan's).
 RNNTStatus make_joint_path_plan(const mrnnt_joint_problem *jp, int num_paths, JointPathPlan *pp) {
-    if (jp && jp->alignment)
-        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL: "
-                                               "the band arrays hold the hull of the given paths)");
-    if (num_paths < 1)
-        return fail(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
-    const RNNTStatus st = make_joint_plan(jp, &pp->jl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = pp->jl.base;
-    if ((int64_t)pl.B * num_paths > 0x7fffffff || pl.B > 65535)
-        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take B <= 65535 and B * num_paths < 2^31");
+    const RNNTStatus st =
+        plan_paths(jp && jp->alignment, num_paths, pl, [&] { return make_joint_plan(jp, &pp->jl); });
+    if (st != RNNT_STATUS_SUCCESS) return st;
     pp->row_bound = 0;
-    for (int b = 0; b < jp->B; ++b) {
-        const int T = jp->T_host[b], S = jp->S_host[b];
-        int64_t inband = 0;
-        for (int t = 0; t < T; ++t) inband += std::min(t, S) - std::max(0, t - (T - S)) + 1;
-        pp->row_bound += std::min<int64_t>((int64_t)num_paths * T, inband);
-    }
-    size_t o = pp->jl.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
-    pp->off_min = take(sizeof(int) * (size_t)pl.cols);
-    pp->off_max = take(sizeof(int) * (size_t)pl.cols);
-    pp->off_valid = take(sizeof(int) * (size_t)pl.B * num_paths);
-    pp->off_carry = take(sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
-    pp->total = o;
+    for (int b = 0; b < jp->B; ++b)
+        pp->row_bound += std::min<int64_t>((int64_t)num_paths * jp->T_host[b], inband_rows(jp->T_host[b], jp->S_host[b]));
+    Carver c{pp->jl.total};
+    pp->off_min = c.take(sizeof(int) * (size_t)pl.cols);
+    pp->off_max = c.take(sizeof(int) * (size_t)pl.cols);
+    pp->off_valid = c.take(sizeof(int) * (size_t)pl.B * num_paths);
+    pp->off_carry = c.take(sizeof(int) * (size_t)path_carry_slots(pl.cols, pl.B) * num_paths);
+    pp->total = c.at;
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -219,35 +204,19 @@ PathArgs joint_path_args(const JointPathPlan &pp, void *ws, const int *alignment
 // coefficient launch. mrnnt_joint_reduce / _reduce_pre / _dpre work on it unchanged, as on the path workspace.
 struct JointExpectPlan {
     JointPlan jl;
-    size_t off_A = 0, off_Bk = 0, off_R = 0, off_wb = 0, off_we = 0, total = 0;
+    ExpectState state;
+    size_t off_wb = 0, off_we = 0, total = 0;
 };
 
 RNNTStatus make_joint_expect_plan(const mrnnt_joint_problem *jp, JointExpectPlan *ep) {
     const RNNTStatus st = make_joint_plan(jp, &ep->jl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = ep->jl.base;
-    size_t o = ep->jl.total;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
-    ep->off_A = take(sizeof(double) * (size_t)pl.N);
-    ep->off_Bk = take(sizeof(double) * (size_t)pl.N);
-    ep->off_R = take(sizeof(double) * (size_t)pl.B);
-    ep->off_wb = take(sizeof(double) * (size_t)pl.N);
-    ep->off_we = take(sizeof(double) * (size_t)pl.N);
-    ep->total = o;
-    return RNNT_STATUS_SUCCESS;
-}
-
-// the cost arrays' grid [B, grid_T, grid_S1] holds every row (not looked at when neither array is given)
-RNNTStatus check_cost_grid(const Plan &pl, const float *blank_cost_dev, const float *label_cost_dev, int64_t grid_T,
-                           int64_t grid_S1) {
-    if ((blank_cost_dev || label_cost_dev) && (grid_T < pl.T_max || grid_S1 < (int64_t)pl.S_max + 1))
-        return fail(RNNT_STATUS_INVALID_VALUE, "cost grid [" + std::to_string(grid_T) + ", " + std::to_string(grid_S1) +
-                                                   "] smaller than [max T, max S + 1] = [" + std::to_string(pl.T_max) +
-                                                   ", " + std::to_string(pl.S_max + 1) + "]");
+    Carver c{ep->jl.total};
+    ep->state.carve_from(&c, pl);
+    ep->off_wb = c.take(sizeof(double) * (size_t)pl.N);
+    ep->off_we = c.take(sizeof(double) * (size_t)pl.N);
+    ep->total = c.at;
     return RNNT_STATUS_SUCCESS;
 }
 
@@ -257,11 +226,7 @@ RNNTStatus check_cost_grid(const Plan &pl, const float *blank_cost_dev, const fl
 DevProblem joint_expect_dev(const mrnnt_problem *p, const JointExpectPlan &ep, void *ws, const float *blank_cost_dev,
                             const float *label_cost_dev, int64_t grid_T, int64_t grid_S1) {
     DevProblem d = make_dev(p, ep.jl.base, ws);
-    d.ex_A = carve<double>(ws, ep.off_A);
-    d.ex_Bk = carve<double>(ws, ep.off_Bk);
-    d.ex_R = carve<double>(ws, ep.off_R);
-    d.ex_wb = blank_cost_dev;
-    d.ex_we = label_cost_dev;
+    ep.state.bind(&d, ws, blank_cost_dev, label_cost_dev);
     if (blank_cost_dev || label_cost_dev) {
         d.pad_T = grid_T;
         d.pad_S1 = grid_S1;
@@ -366,12 +331,7 @@ RNNTStatus joint_align_impl(const mrnnt_joint_problem *jp, void *ws, size_t ws_b
 extern "C" {
 
 RNNTStatus mrnnt_joint_workspace_size(const mrnnt_joint_problem *jp, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    JointPlan jl;
-    const RNNTStatus st = make_joint_plan(jp, &jl);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = jl.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<JointPlan>(bytes, [&](JointPlan *jl) { return make_joint_plan(jp, jl); });
 }
 
 RNNTStatus mrnnt_joint_row_bound(const mrnnt_joint_problem *jp, int64_t *rows) {
@@ -410,10 +370,8 @@ RNNTStatus mrnnt_joint_posteriors(const mrnnt_joint_problem *jp, const void *ws,
     RNNTStatus st = make_joint_plan(jp, &jl);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = jl.base;
-    if ((blank_post_dev || label_post_dev) && (grid_T < pl.T_max || grid_S1 < (int64_t)pl.S_max + 1))
-        return fail(RNNT_STATUS_INVALID_VALUE, "posterior grid [" + std::to_string(grid_T) + ", " +
-                                                   std::to_string(grid_S1) + "] smaller than [max T, max S + 1] = [" +
-                                                   std::to_string(pl.T_max) + ", " + std::to_string(pl.S_max + 1) + "]");
+    if ((st = check_grid(pl, blank_post_dev || label_post_dev, "posterior", grid_T, grid_S1)) != RNNT_STATUS_SUCCESS)
+        return st;
     if (emit_dev && (st = check_row_stride("emit", emit_stride, "input", pl.T_max, false, 0)) != RNNT_STATUS_SUCCESS)
         return st;
     if (label_time_dev &&
@@ -470,12 +428,7 @@ RNNTStatus mrnnt_joint_hat_backward(const mrnnt_joint_problem *jp, void *ws, int
 }
 
 RNNTStatus mrnnt_joint_path_workspace_size(const mrnnt_joint_problem *jp, int num_paths, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    JointPathPlan pp;
-    const RNNTStatus st = make_joint_path_plan(jp, num_paths, &pp);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = pp.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<JointPathPlan>(bytes, [&](JointPathPlan *pp) { return make_joint_path_plan(jp, num_paths, pp); });
 }
 
 RNNTStatus mrnnt_joint_path_row_bound(const mrnnt_joint_problem *jp, int num_paths, int64_t *rows) {
@@ -508,19 +461,7 @@ RNNTStatus mrnnt_joint_path_forward(const mrnnt_joint_problem *jp, void *ws, siz
     if (e != hipSuccess) return fail_hip(e, "path walk kernels");
     // the hull rows, listed through the alignment window (mode 0); their number stays on the device. No lp zero fill:
     // no recursion runs, and the score kernel reads lp along the valid walks only -- rows of the hull
-    unsigned long long *total = carve<unsigned long long>(ws, jl.off_total);
-    e = launch_row_list(d, 0, carve<int64_t>(ws, jl.off_cnt), carve<int>(ws, jl.off_lcol), carve<int>(ws, jl.off_ls),
-                        total, stream);
-    if (e != hipSuccess) return fail_hip(e, "row list kernels");
-    JointArgs j = joint_args(jp, jl, ws, jl.n_inband);
-    j.n_dev = total;
-    int *wplain = carve<int>(ws, jl.off_wplain);
-    j.wplain = wplain;
-    e = timed(K_JOINT_FWD, stream, [&] {
-        const hipError_t eb = launch_joint_wbound(j.W, j.bias, jp->V, jp->H, wplain, stream);
-        return eb != hipSuccess ? eb : launch_joint_forward(d, j, stream);
-    });
-    if (e != hipSuccess) return fail_hip(e, "joint log-softmax kernel");
+    if ((st = joint_forward_pass(jp, jl, ws, d, true, stream)) != RNNT_STATUS_SUCCESS) return st;
     if (path_costs_dev) {
         e = timed(K_DP, stream, [&] { return launch_path_score(d, a, stream); });
         if (e != hipSuccess) return fail_hip(e, "path score kernel");
@@ -557,12 +498,7 @@ RNNTStatus mrnnt_joint_path_backward(const mrnnt_joint_problem *jp, void *ws, in
 }
 
 RNNTStatus mrnnt_joint_expect_workspace_size(const mrnnt_joint_problem *jp, size_t *bytes) {
-    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
-    JointExpectPlan ep;
-    const RNNTStatus st = make_joint_expect_plan(jp, &ep);
-    if (st != RNNT_STATUS_SUCCESS) return st;
-    *bytes = ep.total;
-    return RNNT_STATUS_SUCCESS;
+    return plan_total<JointExpectPlan>(bytes, [&](JointExpectPlan *ep) { return make_joint_expect_plan(jp, ep); });
 }
 
 RNNTStatus mrnnt_joint_expect_forward(const mrnnt_joint_problem *jp, void *ws, size_t ws_bytes,
@@ -573,7 +509,7 @@ RNNTStatus mrnnt_joint_expect_forward(const mrnnt_joint_problem *jp, void *ws, s
     RNNTStatus st = make_joint_expect_plan(jp, &ep);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const Plan &pl = ep.jl.base;
-    if ((st = check_cost_grid(pl, blank_cost_dev, label_cost_dev, grid_T, grid_S1)) != RNNT_STATUS_SUCCESS) return st;
+    if ((st = check_grid(pl, blank_cost_dev || label_cost_dev, "cost", grid_T, grid_S1)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;
     if ((st = check_workspace(ws, ws_bytes, ep.total)) != RNNT_STATUS_SUCCESS) return st;
     // the joint's forward on the head of the workspace (its own plan: the same offsets), beta only for a gradient
@@ -595,7 +531,7 @@ RNNTStatus mrnnt_joint_expect_rows(const mrnnt_joint_problem *jp, void *ws, size
     RNNTStatus st = make_joint_expect_plan(jp, &ep);
     if (st != RNNT_STATUS_SUCCESS) return st;
     const JointPlan &jl = ep.jl;
-    if ((st = check_cost_grid(jl.base, blank_cost_dev, label_cost_dev, grid_T, grid_S1)) != RNNT_STATUS_SUCCESS)
+    if ((st = check_grid(jl.base, blank_cost_dev || label_cost_dev, "cost", grid_T, grid_S1)) != RNNT_STATUS_SUCCESS)
         return st;
     if (!count_dev) return fail(RNNT_STATUS_INVALID_VALUE, "count is null");
     if ((st = check_joint_pointers(jp)) != RNNT_STATUS_SUCCESS) return st;

@@ -182,34 +182,29 @@ RNNTStatus make_plan(const mrnnt_problem *p, Plan *pl, bool band) {
                                                    (q.pad_S1 ? "padded layout needs " : "lattice needs sum_b T_b(S_b+1) = ") +
                                                    std::to_string(acts_rows));
     q.align = p->alignment != nullptr || band;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o = align_up(o + bytes);
-        return at;
-    };
-    q.off_row = take(sizeof(int64_t) * (q.B + 1));
-    q.off_col = take(sizeof(int64_t) * (q.B + 1));
-    q.off_colb = take(sizeof(int) * q.cols);
-    q.off_den = take(sizeof(float) * q.N);
-    q.off_lp = take(sizeof(Lp) * (q.N + 2 * kLpPad));
-    q.off_alpha = take(sizeof(double) * q.N);
-    q.off_beta = take(sizeof(double) * q.N);
-    q.off_ll = take(sizeof(double) * q.B);
-    q.off_llb = take(sizeof(double) * q.B);
+    Carver c;
+    q.off_row = c.take(sizeof(int64_t) * (q.B + 1));
+    q.off_col = c.take(sizeof(int64_t) * (q.B + 1));
+    q.off_colb = c.take(sizeof(int) * q.cols);
+    q.off_den = c.take(sizeof(float) * q.N);
+    q.off_lp = c.take(sizeof(Lp) * (q.N + 2 * kLpPad));
+    q.off_alpha = c.take(sizeof(double) * q.N);
+    q.off_beta = c.take(sizeof(double) * q.N);
+    q.off_ll = c.take(sizeof(double) * q.B);
+    q.off_llb = c.take(sizeof(double) * q.B);
     // the alignment band after the per-row state, so the state's offsets do not depend on the alignment flag (the
     // C++ manager's band getter rebuilds the band in a workspace that holds the state of an earlier computation)
-    q.off_mtmp = q.align ? take(sizeof(int) * (q.cols + q.B)) : 0;
-    q.off_min = q.align ? take(sizeof(int) * q.cols) : 0;
-    q.off_max = q.align ? take(sizeof(int) * q.cols) : 0;
-    q.off_dyn = q.dyn ? take(sizeof(DynWords)) : 0;
+    q.off_mtmp = q.align ? c.take(sizeof(int) * (q.cols + q.B)) : 0;
+    q.off_min = q.align ? c.take(sizeof(int) * q.cols) : 0;
+    q.off_max = q.align ? c.take(sizeof(int) * q.cols) : 0;
+    q.off_dyn = q.dyn ? c.take(sizeof(DynWords)) : 0;
     // the chase launch's ready flags (mrnnt_chase.hip), one word per column (device lengths: per column of the bound),
     // for problems whose shape can take it -- last, so no other offset depends on it
     if (chase_shape_ok(q)) {
         q.flags_bytes = sizeof(unsigned long long) * (size_t)q.cols;
-        q.off_flags = take(q.flags_bytes);
+        q.off_flags = c.take(q.flags_bytes);
     }
-    q.total = o;
+    q.total = c.at;
     *pl = q;
     return RNNT_STATUS_SUCCESS;
 }
@@ -439,6 +434,34 @@ PathArgs path_args(void *ws, size_t off_valid, size_t off_carry, size_t off_min,
     a.costs = nullptr;
     a.w = nullptr;
     return a;
+}
+
+int64_t inband_rows(int T, int S) {
+    int64_t n = 0;
+    for (int t = 0; t < T; ++t) n += std::min(t, S) - std::max(0, t - (T - S)) + 1;
+    return n;
+}
+
+void ExpectState::carve_from(Carver *c, const Plan &pl) {
+    off_A = c->take(sizeof(double) * (size_t)pl.N);
+    off_Bk = c->take(sizeof(double) * (size_t)pl.N);
+    off_R = c->take(sizeof(double) * (size_t)pl.B);
+}
+
+void ExpectState::bind(DevProblem *d, void *ws, const float *blank_cost_dev, const float *label_cost_dev) const {
+    d->ex_A = carve<double>(ws, off_A);
+    d->ex_Bk = carve<double>(ws, off_Bk);
+    d->ex_R = carve<double>(ws, off_R);
+    d->ex_wb = blank_cost_dev;
+    d->ex_we = label_cost_dev;
+}
+
+RNNTStatus check_grid(const Plan &pl, bool given, const char *noun, int64_t grid_T, int64_t grid_S1) {
+    if (given && (grid_T < pl.T_max || grid_S1 < (int64_t)pl.S_max + 1))
+        return fail(RNNT_STATUS_INVALID_VALUE, std::string(noun) + " grid [" + std::to_string(grid_T) + ", " +
+                                                   std::to_string(grid_S1) + "] smaller than [max T, max S + 1] = [" +
+                                                   std::to_string(pl.T_max) + ", " + std::to_string(pl.S_max + 1) + "]");
+    return RNNT_STATUS_SUCCESS;
 }
 
 // ---- profiling ---------------------------------------------------------------------------------

@@ -22,6 +22,29 @@ RNNTStatus fail_hip(hipError_t e, const char *where);
 
 size_t align_up(size_t x);  // to the workspace's 256-byte granule
 
+// Carves a workspace: take(bytes) is the offset of the next array (each on the granule), `at` ends as the total.
+struct Carver {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t off = at;
+        at = align_up(at + bytes);
+        return off;
+    }
+};
+
+// A *_workspace_size entry point: the total of the plan that `make` fills.
+template <class PlanT, class F>
+RNNTStatus plan_total(size_t *bytes, F &&make) {
+    if (!bytes) return fail(RNNT_STATUS_INVALID_VALUE, "null size pointer");
+    PlanT pl;
+    const RNNTStatus st = make(&pl);
+    if (st == RNNT_STATUS_SUCCESS) *bytes = pl.total;
+    return st;
+}
+
+// Rows of one utterance inside the monotonic band: sum_t min(t, S) - max(0, t - (T - S)) + 1.
+int64_t inband_rows(int T, int S);
+
 // Launch plan of one problem. With host lengths every size is exact. With device-resident lengths
 // (lengths_on_device) the host plans from bounds it knows without a read-back: N = the rows of acts (packed: exact,
 // checked on the device; padded: B*pad_T*pad_S1), cols <= N (packed; every column holds >= 1 row) or B*pad_T
@@ -112,6 +135,34 @@ RNNTStatus sample_readout(const mrnnt_problem *p, const Plan &pl, const void *ws
 RNNTStatus check_paths(const Plan &pl, const int *alignments_dev, int64_t path_stride);
 PathArgs path_args(void *ws, size_t off_valid, size_t off_carry, size_t off_min, size_t off_max,
                    const int *alignments_dev, int num_paths, int64_t path_stride);
+
+// The preconditions of the path entry points around the plan `make` fills into pl, in their order: no restricting
+// alignment, num_paths >= 1, the plan's own checks, then the batch limits of the path kernels.
+template <class F>
+RNNTStatus plan_paths(bool restricted, int num_paths, const Plan &pl, F &&make) {
+    if (restricted)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take no restricting alignment (p->alignment must be NULL: "
+                                               "the band arrays hold the hull of the given paths)");
+    if (num_paths < 1)
+        return fail(RNNT_STATUS_INVALID_VALUE, "num_paths must be >= 1, got " + std::to_string(num_paths));
+    const RNNTStatus st = make();
+    if (st != RNNT_STATUS_SUCCESS) return st;
+    if ((int64_t)pl.B * num_paths > 0x7fffffff || pl.B > 65535)
+        return fail(RNNT_STATUS_INVALID_VALUE, "path scores take B <= 65535 and B * num_paths < 2^31");
+    return RNNT_STATUS_SUCCESS;
+}
+
+// mrnnt_expect_* / mrnnt_joint_expect_*: the expectation state A / Bk (fp64 [N]) and R (fp64 [B]) carved after a
+// plan's own arrays, and the device problem's view of it and of the caller's cost arrays.
+struct ExpectState {
+    size_t off_A = 0, off_Bk = 0, off_R = 0;
+    void carve_from(Carver *c, const Plan &pl);
+    void bind(DevProblem *d, void *ws, const float *blank_cost_dev, const float *label_cost_dev) const;
+};
+
+// A caller's grid [B, grid_T, grid_S1] holds every row of the lattice (not looked at unless `given`):
+// "<noun> grid [..] smaller than [max T, max S + 1] = [..]"
+RNNTStatus check_grid(const Plan &pl, bool given, const char *noun, int64_t grid_T, int64_t grid_S1);
 
 // ---- profiling (mrnnt_profile_enable / mrnnt_profile_read) ------------------------------------------------------
 struct ProfRec {

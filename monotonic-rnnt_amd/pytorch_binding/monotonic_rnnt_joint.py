@@ -44,10 +44,12 @@ import torch
 
 try:
     from . import _mrnnt_lib as _L
-    from .monotonic_rnnt_op import Posteriors, Samples, _check_labels, _lengths, _sample_args
+    from .monotonic_rnnt_op import (Posteriors, Samples, _check_labels, _lengths, _path_alignments, _sample_args,
+                                    _upstream)
 except ImportError:
     import _mrnnt_lib as _L
-    from monotonic_rnnt_op import Posteriors, Samples, _check_labels, _lengths, _sample_args
+    from monotonic_rnnt_op import (Posteriors, Samples, _check_labels, _lengths, _path_alignments, _sample_args,
+                                   _upstream)
 
 _L.load()
 
@@ -118,12 +120,16 @@ class _JointPrepared:
     def stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _workspace(self, size, name, *args):
+        """A fresh workspace of size(problem, *args, &bytes) bytes."""
+        n = ctypes.c_size_t(0)
+        _L.check(size(ctypes.byref(self.problem), *args, ctypes.byref(n)), name)
+        return torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+
     def forward(self, with_beta: bool):
         lib = _L.load()
-        n = ctypes.c_size_t(0)
-        _L.check(lib.mrnnt_joint_workspace_size(ctypes.byref(self.problem), ctypes.byref(n)), "joint_workspace_size")
         with torch.cuda.device(self.device):
-            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(lib.mrnnt_joint_workspace_size, "joint_workspace_size")
             costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
             fwd, name = ((lib.mrnnt_joint_hat_forward, "mrnnt_joint_hat_forward") if self.hat
                          else (lib.mrnnt_joint_forward, "mrnnt_joint_forward"))
@@ -134,10 +140,8 @@ class _JointPrepared:
     def align(self, L: int):
         """(alignment int32 [B, L], costs [B]): mrnnt_joint_align on a workspace of its own."""
         lib = _L.load()
-        n = ctypes.c_size_t(0)
-        _L.check(lib.mrnnt_joint_workspace_size(ctypes.byref(self.problem), ctypes.byref(n)), "joint_workspace_size")
         with torch.cuda.device(self.device):
-            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(lib.mrnnt_joint_workspace_size, "joint_workspace_size")
             out = torch.empty((self.B, L), dtype=torch.int32, device=self.device)
             costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
             align, name = ((lib.mrnnt_joint_hat_align, "mrnnt_joint_hat_align") if self.hat
@@ -182,30 +186,41 @@ class _JointPrepared:
             cnt = torch.zeros(1, dtype=torch.int64, device=self.device)
             _L.check(lib.mrnnt_joint_live_rows(ctypes.byref(self.problem), _vp(ws), _vp(cnt), self.stream()),
                      "mrnnt_joint_live_rows")
-            if capturable:
-                nb = ctypes.c_int64(0)
-                _L.check(lib.mrnnt_joint_row_bound(ctypes.byref(self.problem), ctypes.byref(nb)), "joint_row_bound")
-                n = nb.value
-                self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
-                self.problem.live_count_dev = cnt.data_ptr()
-            else:
-                n = int(cnt.item())  # one 8-byte read-back sizes the row buffers
-                self.problem.live_count_dev = None
-            G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
-            ld = _HACT_LD[self.H] if bias_column else self.H
-            self.problem.hact_ld = ld  # mrnnt_joint_reduce reads Hact with the same stride
-            Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
-            bt = bs = None
-            if with_index:
-                bt = torch.empty(max(1, n), dtype=torch.int64, device=self.device)
-                bs = torch.empty(max(1, n), dtype=torch.int64, device=self.device)
-            if grad_scale is not None:
-                grad_scale = grad_scale.detach().to(self.device, torch.float32).contiguous()
-            self.problem.dbias = _vp(dbias)  # the gradient pass adds sum_i G[i] into it (zeroed by the caller)
             bwd, name = ((lib.mrnnt_joint_hat_backward, "mrnnt_joint_hat_backward") if self.hat
                          else (lib.mrnnt_joint_backward, "mrnnt_joint_backward"))
-            _L.check(bwd(ctypes.byref(self.problem), _vp(ws), n, _vp(grad_scale), _vp(G), _vp(Hact), _vp(bt), _vp(bs),
-                         self.stream()), name)
+            return self._rows_backward(ws, cnt, self.row_bound() if capturable else None, bwd, name,
+                                       (_vp(_upstream(grad_scale, self)),), with_index, bias_column, dbias)
+
+    def row_bound(self):
+        nb = ctypes.c_int64(0)
+        _L.check(_L.load().mrnnt_joint_row_bound(ctypes.byref(self.problem), ctypes.byref(nb)), "joint_row_bound")
+        return nb.value
+
+    def _rows_backward(self, ws, cnt, bound, bwd, name, lead=(), with_index=False, bias_column=False, dbias=None):
+        """The gradient pass bwd (entry point `name`) over the rows of the last list built, cnt (int64 [1], on the
+        device) of them: sizes and fills the row buffers (G [n, V], Hact [n, H or _HACT_LD[H]] and, with_index,
+        bt_idx / bs_idx [n]). bound
+        None: one 8-byte read-back of cnt is n; else n is that host-known bound, the kernels take the count from the
+        device and the rows past it are zeros. lead: the entry point's arguments between n and G. Runs on the
+        caller's current device."""
+        if bound is not None:
+            n = bound
+            self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
+            self.problem.live_count_dev = cnt.data_ptr()
+        else:
+            n = int(cnt.item())  # one 8-byte read-back sizes the row buffers
+            self.problem.live_count_dev = None
+        G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
+        ld = _HACT_LD[self.H] if bias_column else self.H
+        self.problem.hact_ld = ld  # mrnnt_joint_reduce reads Hact with the same stride
+        Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
+        bt = bs = None
+        if with_index:
+            bt = torch.empty(max(1, n), dtype=torch.int64, device=self.device)
+            bs = torch.empty(max(1, n), dtype=torch.int64, device=self.device)
+        self.problem.dbias = _vp(dbias)  # the gradient pass adds sum_i G[i] into it (zeroed by the caller)
+        _L.check(bwd(ctypes.byref(self.problem), _vp(ws), n, *lead, _vp(G), _vp(Hact), _vp(bt), _vp(bs), self.stream()),
+                 name)
         if with_index:
             return G[:n], Hact[:n], bt[:n], bs[:n]
         return G[:n], Hact[:n]
@@ -215,11 +230,8 @@ class _JointPrepared:
         contiguous, on the device) on a workspace of mrnnt_joint_path_workspace_size bytes."""
         lib = _L.load()
         K, L = al.size(1), al.size(2)
-        n = ctypes.c_size_t(0)
-        _L.check(lib.mrnnt_joint_path_workspace_size(ctypes.byref(self.problem), K, ctypes.byref(n)),
-                 "joint_path_workspace_size")
         with torch.cuda.device(self.device):
-            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(lib.mrnnt_joint_path_workspace_size, "joint_path_workspace_size", K)
             costs = torch.empty((self.B, K), dtype=torch.float32, device=self.device)
             _L.check(lib.mrnnt_joint_path_forward(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(al), K, L,
                                                   _vp(costs), self.stream()), "mrnnt_joint_path_forward")
@@ -246,24 +258,11 @@ class _JointPrepared:
         default one 8-byte read-back of their count sizes the buffers; capturable: they are sized by the host-known
         bound sum_b min(K T_b, in-band rows) (mrnnt_joint_path_row_bound), the kernels take the count from the device
         and the rows past it are zeros."""
-        lib = _L.load()
         cnt = self.path_rows(ws, al, w)
         with torch.cuda.device(self.device):
-            if capturable:
-                n = self.path_row_bound(al.size(1))
-                self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
-                self.problem.live_count_dev = cnt.data_ptr()
-            else:
-                n = int(cnt.item())
-                self.problem.live_count_dev = None
-            G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
-            ld = _HACT_LD[self.H] if bias_column else self.H
-            self.problem.hact_ld = ld
-            Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
-            self.problem.dbias = _vp(dbias)
-            _L.check(lib.mrnnt_joint_path_backward(ctypes.byref(self.problem), _vp(ws), n, _vp(G), _vp(Hact), None,
-                                                   None, self.stream()), "mrnnt_joint_path_backward")
-        return G[:n], Hact[:n]
+            return self._rows_backward(ws, cnt, self.path_row_bound(al.size(1)) if capturable else None,
+                                       _L.load().mrnnt_joint_path_backward, "mrnnt_joint_path_backward",
+                                       bias_column=bias_column, dbias=dbias)
 
     def cost_grid(self, blank_costs, label_costs):
         """The two per-arc cost arrays as mrnnt_joint_expect_* take them: (wb, we, grid_T, grid_S1), fp32 [B, grid_T,
@@ -289,11 +288,8 @@ class _JointPrepared:
         """(expected [B], costs [B], workspace): mrnnt_joint_expect_forward on a workspace of
         mrnnt_joint_expect_workspace_size bytes."""
         lib = _L.load()
-        n = ctypes.c_size_t(0)
-        _L.check(lib.mrnnt_joint_expect_workspace_size(ctypes.byref(self.problem), ctypes.byref(n)),
-                 "joint_expect_workspace_size")
         with torch.cuda.device(self.device):
-            ws = torch.empty(max(1, n.value), dtype=torch.uint8, device=self.device)
+            ws = self._workspace(lib.mrnnt_joint_expect_workspace_size, "joint_expect_workspace_size")
             expected = torch.empty(self.B, dtype=torch.float32, device=self.device)
             costs = torch.empty(self.B, dtype=torch.float32, device=self.device)
             _L.check(lib.mrnnt_joint_expect_forward(ctypes.byref(self.problem), _vp(ws), ws.numel(), _vp(wb), _vp(we),
@@ -315,26 +311,11 @@ class _JointPrepared:
         """backward_rows for the expected cost: (G [n, V], Hact [n, H or _HACT_LD[H]]) over the expect-live rows. By
         default one 8-byte read-back of their count sizes the buffers; capturable: they are sized by the in-band rows
         (mrnnt_joint_row_bound), the kernels take the count from the device and the rows past it are zeros."""
-        lib = _L.load()
         cnt = self.expect_rows(ws, wb, we, gT, gS1, ge, gc)
         with torch.cuda.device(self.device):
-            if capturable:
-                nb = ctypes.c_int64(0)
-                _L.check(lib.mrnnt_joint_row_bound(ctypes.byref(self.problem), ctypes.byref(nb)), "joint_row_bound")
-                n = nb.value
-                self.live_count = cnt  # referenced by the problem until the backward's last kernel is queued
-                self.problem.live_count_dev = cnt.data_ptr()
-            else:
-                n = int(cnt.item())
-                self.problem.live_count_dev = None
-            G = torch.empty(max(1, n), self.V, dtype=torch.bfloat16, device=self.device)
-            ld = _HACT_LD[self.H] if bias_column else self.H
-            self.problem.hact_ld = ld
-            Hact = torch.empty(max(1, n), ld, dtype=torch.bfloat16, device=self.device)
-            self.problem.dbias = _vp(dbias)
-            _L.check(lib.mrnnt_joint_expect_backward(ctypes.byref(self.problem), _vp(ws), n, _vp(G), _vp(Hact), None,
-                                                     None, self.stream()), "mrnnt_joint_expect_backward")
-        return G[:n], Hact[:n]
+            return self._rows_backward(ws, cnt, self.row_bound() if capturable else None,
+                                       _L.load().mrnnt_joint_expect_backward, "mrnnt_joint_expect_backward",
+                                       bias_column=bias_column, dbias=dbias)
 
     def dpre(self, G, Hact):
         """dpre = (G weight) * (1 - Hact^2), bf16 [n, H], on the library's hand-written MFMA tiles (mrnnt_joint_dpre)."""
@@ -430,6 +411,11 @@ def _split_k_weight_grad(G, Hact, chunks=32):
     if head < n:
         part += torch.mm(G[head:].t(), Hact[head:], out_dtype=torch.float32)
     return part
+
+
+def _cast(x):
+    """x as the joint kernels take it (bfloat16); the cast is differentiable"""
+    return x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
 
 
 def _loss_forward(ctx, hat, enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label, alignment,
@@ -537,8 +523,7 @@ def monotonic_rnnt_joint_loss(enc: torch.Tensor, pred: torch.Tensor, weight: tor
     reads no live-row count back to the host (row buffers and GEMMs sized by the in-band rows instead of the live
     ones: slower, graph-capturable); None = only inside HIP-graph capture (or MRNNT_JOINT_CAPTURABLE=1). A step
     captured with it replays bit for bit what an eager capturable=True step computes."""
-    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
-    return MonotonicRNNTJointFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
+    return MonotonicRNNTJointFunction.apply(_cast(enc), _cast(pred), _cast(weight), bias, labels, input_lengths,
                                             label_lengths, blank_label, alignment, max_distance_from_alignment,
                                             capturable)
 
@@ -560,8 +545,7 @@ def monotonic_rnnt_joint_hat_loss(enc: torch.Tensor, pred: torch.Tensor, weight:
     path (cost +inf) contributes exactly zero to every gradient, so d_weight / d_bias stay finite for the rest of the
     batch; a NaN cost keeps NaN gradients. Costs and gradients are bitwise reproducible. monotonic_rnnt_joint_align / _posteriors / _sample take blank_factorized=True for the same
     distribution; monotonic_rnnt_joint_path_loss / _expected_cost are softmax-only."""
-    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
-    return MonotonicRNNTJointHatFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
+    return MonotonicRNNTJointHatFunction.apply(_cast(enc), _cast(pred), _cast(weight), bias, labels, input_lengths,
                                                label_lengths, blank_label, alignment, max_distance_from_alignment,
                                                capturable)
 
@@ -576,16 +560,7 @@ class MonotonicRNNTJointPathFunction(torch.autograd.Function):
     def forward(ctx, enc, pred, weight, bias, labels, input_lengths, label_lengths, alignments, blank_label=0,
                 capturable=None):
         prep = _JointPrepared(enc, pred, weight, bias, labels, input_lengths, label_lengths, blank_label)
-        al = alignments.detach()
-        if al.device != prep.device or al.dtype != torch.int32:
-            al = al.to(prep.device, torch.int32)
-        if al.dim() != 3 or al.size(0) != prep.B:
-            raise RuntimeError(f"monotonic_rnnt_joint_path_loss: alignments must be [B = {prep.B}, K, L], "
-                               f"got {tuple(al.shape)}")
-        al = al.contiguous()
-        if al.size(1) < 1 or al.size(2) < 1:
-            raise RuntimeError("monotonic_rnnt_joint_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got "
-                               f"{al.size(1)}, {al.size(2)}")
+        al = _path_alignments(alignments, prep.device, prep.B, "monotonic_rnnt_joint_path_loss")
         costs, ws = prep.path_forward(al)
         if any(ctx.needs_input_grad[:4]):
             # the workspace holds den of the hull rows, the hull and the paths' validity
@@ -598,7 +573,7 @@ class MonotonicRNNTJointPathFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_costs):
         prep, ws, al = ctx.prep, ctx.saved_tensors[3], ctx.saved_tensors[4]
-        w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
+        w = _upstream(grad_costs, prep)
         bias_col, fused_b, db = _dbias_plan(ctx, prep)
         G, Hact = prep.path_backward_rows(ws, al, w, bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
         if G.shape[0] == 0:  # no path-live row (all-zero weights, no valid path): every gradient is exactly zero
@@ -641,9 +616,8 @@ def monotonic_rnnt_joint_path_loss(enc: torch.Tensor, pred: torch.Tensor, weight
     writes no dense logit gradient. capturable as in monotonic_rnnt_joint_loss: by default one 8-byte read-back of
     that row count sizes the row buffers; True (or inside HIP-graph capture) sizes them by the host-known bound
     sum_b min(K T_b, in-band rows). Costs and gradients are bitwise reproducible."""
-    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
     al = alignments.unsqueeze(1) if alignments.dim() == 2 else alignments
-    out = MonotonicRNNTJointPathFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels, input_lengths,
+    out = MonotonicRNNTJointPathFunction.apply(_cast(enc), _cast(pred), _cast(weight), bias, labels, input_lengths,
                                                label_lengths, al, blank_label, capturable)
     return out.squeeze(1) if alignments.dim() == 2 else out
 
@@ -674,10 +648,10 @@ class MonotonicRNNTJointExpectedCostFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_expected, grad_costs):
         prep, ws = ctx.prep, ctx.saved_tensors[3]
-        up = lambda g: None if g is None else g.detach().to(prep.device, torch.float32).contiguous()  # noqa: E731
         bias_col, fused_b, db = _dbias_plan(ctx, prep)
-        G, Hact = prep.expect_backward_rows(ws, *ctx.costs_grid, up(grad_expected), up(grad_costs),
-                                            bias_column=bias_col, dbias=db, capturable=_capturable(ctx))
+        G, Hact = prep.expect_backward_rows(ws, *ctx.costs_grid, _upstream(grad_expected, prep),
+                                            _upstream(grad_costs, prep), bias_column=bias_col, dbias=db,
+                                            capturable=_capturable(ctx))
         if G.shape[0] == 0:  # no expect-live row (both upstreams zero, only single-path utterances under g_c = 0)
             return _zero_grads(ctx, prep) + (None,) * 9
         return _grads_from_rows(ctx, prep, ws, G, Hact, bias_col, fused_b, db) + (None,) * 9
@@ -711,15 +685,21 @@ def monotonic_rnnt_joint_expected_cost(enc: torch.Tensor, pred: torch.Tensor, we
     function of the two is one chain over the rows whose coefficients are not both zero. An utterance without a finite
     cost has a NaN expected value and NaN gradients; the others' expected and costs are unaffected. Results are bitwise
     reproducible."""
-    cast = lambda x: x if x is None or x.dtype == torch.bfloat16 else x.to(torch.bfloat16)  # noqa: E731
-    return MonotonicRNNTJointExpectedCostFunction.apply(cast(enc), cast(pred), cast(weight), bias, labels,
+    return MonotonicRNNTJointExpectedCostFunction.apply(_cast(enc), _cast(pred), _cast(weight), bias, labels,
                                                         input_lengths, label_lengths, blank_costs, label_costs,
                                                         blank_label, alignment, max_distance_from_alignment, capturable)
 
 
 def _bf16(x):
-    x = x.detach()
-    return x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
+    return _cast(x.detach())
+
+
+def _frames(prep, max_input_length, who):
+    """Row length of a per-frame output: max_input_length (>= 1), else the longest input length."""
+    L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
+    if L < 1:
+        raise RuntimeError(f"{who}: max_input_length must be >= 1, got {L}")
+    return L
 
 
 def monotonic_rnnt_joint_align(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
@@ -740,10 +720,7 @@ def monotonic_rnnt_joint_align(enc: torch.Tensor, pred: torch.Tensor, weight: to
     of monotonic_rnnt_joint_hat_loss (mrnnt_joint_hat_align). Not differentiable: plain tensors are returned."""
     prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
                           blank_label, alignment, max_distance_from_alignment, hat=blank_factorized)
-    L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
-    if L < 1:
-        raise RuntimeError(f"monotonic_rnnt_joint_align: max_input_length must be >= 1, got {L}")
-    return prep.align(L)
+    return prep.align(_frames(prep, max_input_length, "monotonic_rnnt_joint_align"))
 
 
 def monotonic_rnnt_joint_posteriors(enc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor,
@@ -784,9 +761,7 @@ def monotonic_rnnt_joint_sample(enc: torch.Tensor, pred: torch.Tensor, weight: t
     K, seed, first = _sample_args(num_samples, seed, first_sample, "monotonic_rnnt_joint_sample")
     prep = _JointPrepared(_bf16(enc), _bf16(pred), _bf16(weight), bias, labels, input_lengths, label_lengths,
                           blank_label, alignment, max_distance_from_alignment, hat=blank_factorized)
-    L = int(max_input_length) if max_input_length is not None else int(prep.T_host.max(initial=1))
-    if L < 1:
-        raise RuntimeError(f"monotonic_rnnt_joint_sample: max_input_length must be >= 1, got {L}")
+    L = _frames(prep, max_input_length, "monotonic_rnnt_joint_sample")
     if K < 1:
         raise RuntimeError(f"monotonic_rnnt_joint_sample: num_samples must be >= 1, got {K}")
     return prep.sample(K, seed, first, L)

@@ -284,21 +284,12 @@ class _Prepared:
         n = cache.get(key)
         if n is None:
             c = ctypes.c_size_t(0)
-            if expect:
-                size = _L.load().mrnnt_expect_workspace_size if self.on_gpu else _L.load().mrnnt_cpu_expect_workspace_size
-                with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
-                    _L.check(size(ctypes.byref(self.problem), ctypes.byref(c)), "expect_workspace_size")
-            elif num_paths > 0:
-                size = _L.load().mrnnt_path_workspace_size if self.on_gpu else _L.load().mrnnt_cpu_path_workspace_size
-                with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
-                    _L.check(size(ctypes.byref(self.problem), num_paths, ctypes.byref(c)), "path_workspace_size")
-            elif self.on_gpu:  # the plan reads the CU count of the CURRENT device: make it this call's
-                with _on_device(self.device):
-                    _L.check(_L.load().mrnnt_workspace_size(ctypes.byref(self.problem), ctypes.byref(c)),
-                             "workspace_size")
-            else:
-                _L.check(_L.load().mrnnt_cpu_workspace_size(ctypes.byref(self.problem), ctypes.byref(c)),
-                         "workspace_size")
+            name, args = (("expect_workspace_size", ()) if expect else
+                          ("path_workspace_size", (num_paths,)) if num_paths > 0 else ("workspace_size", ()))
+            size = getattr(_L.load(), ("mrnnt_" if self.on_gpu else "mrnnt_cpu_") + name)
+            # the plan reads the CU count of the CURRENT device: make it this call's
+            with (_on_device(self.device) if self.on_gpu else _NULL_CTX):
+                _L.check(size(ctypes.byref(self.problem), *args, ctypes.byref(c)), name)
             n = cache[key] = max(1, c.value)
             if self.dyn and len(_DYN_WS) > 256:
                 _DYN_WS.clear()
@@ -358,12 +349,23 @@ def _forward(prep: _Prepared, with_beta: bool, hat: bool = False):
     return costs, ws
 
 
-def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tensor],
-              grads: Optional[torch.Tensor] = None, hat: bool = False) -> torch.Tensor:
+def _tracked_backward(prep: _Prepared, stem: str, lead: tuple, grads: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The dense gradient of entry point `stem` (mrnnt_<stem> / mrnnt_cpu_<stem>; lead: its arguments before grads)
+    into grads, or into a buffer of this call's."""
     ticket = None
     if grads is None:  # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), with the
         # state of its rows: the tracked entry does not store again the zero rows the buffer already holds
         grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
+    if ticket is not None:
+        _call(prep, stem + "_tracked", *lead, _ptr(grads), _ptr(ticket.state), ticket.state.numel(), lengths=False)
+        ticket.commit()  # enqueued: the state describes the buffer from here on (in stream order)
+    else:
+        _call(prep, stem, *lead, _ptr(grads), lengths=False)
+    return grads
+
+
+def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tensor],
+              grads: Optional[torch.Tensor] = None, hat: bool = False) -> torch.Tensor:
     prep.problem.grad_scale_broadcast = 0
     if grad_scale is not None:
         grad_scale = grad_scale.detach()
@@ -374,13 +376,22 @@ def _backward(prep: _Prepared, ws: torch.Tensor, grad_scale: Optional[torch.Tens
             prep.problem.grad_scale_broadcast = 1
         else:
             grad_scale = grad_scale.to(prep.device, torch.float32).contiguous()
-    if ticket is not None:
-        _call(prep, "hat_backward_tracked" if hat else "backward_tracked", _ptr(ws), _ptr(grad_scale), _ptr(grads),
-              _ptr(ticket.state), ticket.state.numel(), lengths=False)
-        ticket.commit()  # enqueued: the state describes the buffer from here on (in stream order)
-    else:
-        _call(prep, "hat_backward" if hat else "backward", _ptr(ws), _ptr(grad_scale), _ptr(grads), lengths=False)
-    return grads
+    return _tracked_backward(prep, "hat_backward" if hat else "backward", (_ptr(ws), _ptr(grad_scale)), grads)
+
+
+def _loss_forward(ctx, hat, acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
+                  blank_label):
+    """The forward of MonotonicRNNTFunction (hat = False) and MonotonicRNNTHatFunction (hat = True)."""
+    prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment, blank_label)
+    need_grad = bool(ctx.needs_input_grad[0])
+    costs, ws = _forward(prep, with_beta=need_grad, hat=hat)
+    if need_grad:
+        # acts is re-read by the gradient kernel (saving it lets autograd catch in-place edits); the workspace
+        # (den / lp / alpha / beta) is a saved tensor too, so autograd frees it after the last backward and
+        # keeps it for another one under retain_graph=True (the reference saves its grads, :92)
+        ctx.save_for_backward(acts, ws)
+        ctx.prep, ctx.hat = prep, hat
+    return costs
 
 
 class MonotonicRNNTFunction(torch.autograd.Function):
@@ -390,22 +401,13 @@ class MonotonicRNNTFunction(torch.autograd.Function):
     def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                 label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
                 max_distance_from_alignment: int = 0, blank_label: int = 0) -> torch.Tensor:
-        prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
-                         blank_label)
-        need_grad = bool(ctx.needs_input_grad[0])
-        costs, ws = _forward(prep, with_beta=need_grad)
-        if need_grad:
-            # acts is re-read by the gradient kernel (saving it lets autograd catch in-place edits); the workspace
-            # (den / lp / alpha / beta) is a saved tensor too, so autograd frees it after the last backward and
-            # keeps it for another one under retain_graph=True (the reference saves its grads, :92)
-            ctx.save_for_backward(acts, ws)
-            ctx.prep = prep
-        return costs
+        return _loss_forward(ctx, False, acts, labels, input_lengths, label_lengths, alignment,
+                             max_distance_from_alignment, blank_label)
 
     @staticmethod
     def backward(ctx, grad_outputs):
         _, ws = ctx.saved_tensors
-        grads = _backward(ctx.prep, ws, grad_outputs)
+        grads = _backward(ctx.prep, ws, grad_outputs, hat=ctx.hat)
         return grads, None, None, None, None, None, None
 
 
@@ -435,29 +437,18 @@ def monotonic_rnnt_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths:
     return result
 
 
-class MonotonicRNNTHatFunction(torch.autograd.Function):
+class MonotonicRNNTHatFunction(MonotonicRNNTFunction):
     """The loss with the factorised blank of the hybrid autoregressive transducer (mrnnt_hat_forward /
     mrnnt_hat_backward and the mrnnt_cpu_hat_* twins, include/mrnnt.h): apply(acts, labels, input_lengths,
-    label_lengths, alignment=None, max_distance_from_alignment=0, blank_label=0) -> costs [B]."""
+    label_lengths, alignment=None, max_distance_from_alignment=0, blank_label=0) -> costs [B]. The backward is
+    MonotonicRNNTFunction's (the context remembers the flavour)."""
 
     @staticmethod
     def forward(ctx, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                 label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
                 max_distance_from_alignment: int = 0, blank_label: int = 0) -> torch.Tensor:
-        prep = _Prepared(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
-                         blank_label)
-        need_grad = bool(ctx.needs_input_grad[0])
-        costs, ws = _forward(prep, with_beta=need_grad, hat=True)
-        if need_grad:  # (acts and the workspace: as MonotonicRNNTFunction)
-            ctx.save_for_backward(acts, ws)
-            ctx.prep = prep
-        return costs
-
-    @staticmethod
-    def backward(ctx, grad_outputs):
-        _, ws = ctx.saved_tensors
-        grads = _backward(ctx.prep, ws, grad_outputs, hat=True)
-        return grads, None, None, None, None, None, None
+        return _loss_forward(ctx, True, acts, labels, input_lengths, label_lengths, alignment,
+                             max_distance_from_alignment, blank_label)
 
 
 def monotonic_rnnt_hat_loss(acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
@@ -630,6 +621,24 @@ def monotonic_rnnt_sample(acts: torch.Tensor, labels: torch.Tensor, input_length
     return Samples(out, path_costs, costs)
 
 
+def _path_alignments(alignments: torch.Tensor, dev: torch.device, B: int, who: str) -> torch.Tensor:
+    """The alignment rows as the path entry points take them: int32 [B, K >= 1, L >= 1], contiguous, on dev."""
+    al = alignments.detach()
+    if al.device != dev or al.dtype != torch.int32:
+        al = al.to(dev, torch.int32)
+    if al.dim() != 3 or al.size(0) != B:
+        raise RuntimeError(f"{who}: alignments must be [B = {B}, K, L], got {tuple(al.shape)}")
+    al = al.contiguous()
+    if al.size(1) < 1 or al.size(2) < 1:
+        raise RuntimeError(f"{who}: alignments needs K >= 1 paths of L >= 1 frames, got {al.size(1)}, {al.size(2)}")
+    return al
+
+
+def _upstream(g: Optional[torch.Tensor], prep) -> Optional[torch.Tensor]:
+    """An upstream gradient as the backward entry points take it: float32, contiguous, on the call's device."""
+    return None if g is None else g.detach().to(prep.device, torch.float32).contiguous()
+
+
 class MonotonicRNNTPathFunction(torch.autograd.Function):
     """Scores of given alignments with their logit gradient (mrnnt_path_forward / mrnnt_path_backward and the
     mrnnt_cpu_path_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, alignments,
@@ -643,15 +652,8 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
         prep = _Prepared(acts, labels, input_lengths, label_lengths, None, 0, blank_label)
         hat = "hat_" if blank_factorized else ""
         B, dev = prep.problem.B, prep.device
-        al = alignments.detach()
-        if al.device != dev or al.dtype != torch.int32:
-            al = al.to(dev, torch.int32)
-        if al.dim() != 3 or al.size(0) != B:
-            raise RuntimeError(f"monotonic_rnnt_path_loss: alignments must be [B = {B}, K, L], got {tuple(al.shape)}")
-        al = al.contiguous()
+        al = _path_alignments(alignments, dev, B, "monotonic_rnnt_path_loss")
         K, L = al.size(1), al.size(2)
-        if K < 1 or L < 1:
-            raise RuntimeError(f"monotonic_rnnt_path_loss: alignments needs K >= 1 paths of L >= 1 frames, got {K}, {L}")
         ws = prep.workspace(num_paths=K)
         costs = torch.empty((B, K), dtype=torch.float32, device=dev)
         _call(prep, hat + "path_forward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(costs), pending=True)
@@ -667,16 +669,8 @@ class MonotonicRNNTPathFunction(torch.autograd.Function):
         _, ws, al = ctx.saved_tensors
         prep, hat = ctx.prep, ctx.hat
         K, L = al.size(1), al.size(2)
-        w = grad_costs.detach().to(prep.device, torch.float32).contiguous()
-        # large GPU gradients: a fast-writing buffer, kept across calls (_grads_placement), as the loss's
-        grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
-        if ticket is not None:  # (the row state, as the loss's _backward)
-            _call(prep, hat + "path_backward_tracked", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
-                  _ptr(ticket.state), ticket.state.numel(), lengths=False)
-            ticket.commit()
-        else:
-            _call(prep, hat + "path_backward", _ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w), _ptr(grads),
-                  lengths=False)
+        w = _upstream(grad_costs, prep)
+        grads = _tracked_backward(prep, hat + "path_backward", (_ptr(ws), ws.numel(), _ptr(al), K, L, _ptr(w)))
         return grads, None, None, None, None, None, None
 
 
@@ -728,10 +722,6 @@ def _cost_array(x: Optional[torch.Tensor], prep: _Prepared, what: str) -> Option
     return x.detach().to(prep.device, torch.float32).contiguous()
 
 
-def _upstream(g: Optional[torch.Tensor], prep: _Prepared) -> Optional[torch.Tensor]:
-    return None if g is None else g.detach().to(prep.device, torch.float32).contiguous()
-
-
 class MonotonicRNNTExpectedCostFunction(torch.autograd.Function):
     """Expected path costs and the loss with their logit gradient (mrnnt_expect_forward / mrnnt_expect_backward and the
     mrnnt_cpu_expect_* twins, include/mrnnt.h): apply(acts, labels, input_lengths, label_lengths, blank_costs,
@@ -767,15 +757,8 @@ class MonotonicRNNTExpectedCostFunction(torch.autograd.Function):
         _, ws = ctx.saved_tensors
         prep, hat = ctx.prep, ctx.hat
         ge, gc = _upstream(grad_expected, prep), _upstream(grad_costs, prep)
-        # the tracked, placement-probed buffer of the loss's backward (_grads_placement)
-        grads, ticket = _GP.grads_tracked(prep.acts) if prep.on_gpu else (torch.empty_like(prep.acts), None)
-        if ticket is not None:
-            _call(prep, hat + "expect_backward_tracked", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge),
-                  _ptr(gc), _ptr(grads), _ptr(ticket.state), ticket.state.numel(), lengths=False)
-            ticket.commit()
-        else:
-            _call(prep, hat + "expect_backward", _ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc),
-                  _ptr(grads), lengths=False)
+        grads = _tracked_backward(prep, hat + "expect_backward",
+                                  (_ptr(ws), ws.numel(), _ptr(ctx.wb), _ptr(ctx.we), _ptr(ge), _ptr(gc)))
         return grads, None, None, None, None, None, None, None, None, None
 
 
@@ -823,10 +806,12 @@ def monotonic_rnnt_expected_cost(acts: torch.Tensor, labels: torch.Tensor, input
 class MonotonicRNNTLoss(torch.nn.Module):
     """reference monotonic_rnnt_op.py:166-217 (with the self.blank -> self.blank_label fix)."""
 
+    function = MonotonicRNNTFunction
+
     def __init__(self, blank_label: int = 0) -> None:
         super().__init__()
         self.blank_label = blank_label
-        self.loss = MonotonicRNNTFunction.apply
+        self.loss = self.function.apply
 
     def forward(self, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
                 label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
@@ -837,21 +822,10 @@ class MonotonicRNNTLoss(torch.nn.Module):
         return loss
 
 
-class MonotonicRNNTHatLoss(torch.nn.Module):
+class MonotonicRNNTHatLoss(MonotonicRNNTLoss):
     """monotonic_rnnt_hat_loss as a module, in the shape of MonotonicRNNTLoss."""
 
-    def __init__(self, blank_label: int = 0) -> None:
-        super().__init__()
-        self.blank_label = blank_label
-        self.loss = MonotonicRNNTHatFunction.apply
-
-    def forward(self, acts: torch.Tensor, labels: torch.Tensor, input_lengths: torch.Tensor,
-                label_lengths: torch.Tensor, alignment: Optional[torch.Tensor] = None,
-                max_distance_from_alignment: int = 0) -> torch.Tensor:
-        loss = self.loss(acts, labels, input_lengths, label_lengths, alignment, max_distance_from_alignment,
-                         self.blank_label)
-        assert loss is not None
-        return loss
+    function = MonotonicRNNTHatFunction
 
 
 class _Ext:

@@ -105,3 +105,49 @@ def knobs(**kv):
         finally:
             for k, v in saved.items():
                 L.tune(k, v)
+
+
+def check_gradient_in_place(op, stem):
+    """The mrnnt_cpu_<stem>backward entry points document "grads may be acts itself": the gradient written over a copy
+    of acts equals, bit for bit, the one written into a separate buffer. stem: "hat_", "expect_", "hat_path_",
+    "hat_expect_". The smallest shape with every branch of a row -- an utterance with S = T, one with S = 0, a blank
+    index that is not 0, rows with and without a label arc -- packed, then padded (pad_T = 6, pad_S1 = 5)."""
+    import ctypes
+
+    import torch
+    T, S, V, blank, K = np.array([5, 3, 2], np.int32), np.array([2, 3, 0], np.int32), 6, 2, 2
+    rng = np.random.default_rng(5)
+    labels = rng.integers(0, V - 1, (3, 3)).astype(np.int32)
+    labels[labels >= blank] += 1
+    paths = np.full((3, K, 5), blank, np.int32)  # labels first; labels last
+    for b in range(3):
+        paths[b, 0, :S[b]] = labels[b, :S[b]]
+        paths[b, 1, T[b] - S[b]:T[b]] = labels[b, :S[b]]
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data)
+    for shape in ((int(np.sum(T * (S + 1))), V), (3, 6, 5, V)):
+        acts = rng.standard_normal(shape).astype(np.float32)
+        rows = acts.size // V
+        bc, lc = rng.standard_normal(rows).astype(np.float32), rng.standard_normal(rows).astype(np.float32)
+        up = rng.standard_normal((3, K)).astype(np.float32)
+        u0, u1 = up[:, 0].copy(), up[:, 1].copy()
+        got = []
+        for in_place in (False, True):
+            buf = torch.from_numpy(acts.copy())
+            prep = op._Prepared(buf, torch.from_numpy(labels), torch.from_numpy(T), torch.from_numpy(S), None, 0, blank)
+            ws = prep.workspace(num_paths=K if "path" in stem else 0, expect="expect" in stem)
+            grads = buf if in_place else torch.empty_like(buf)
+            w = (op._ptr(ws), ws.numel())
+            if "path" in stem:
+                args = (*w, vp(paths), K, paths.shape[2])
+                op._call(prep, stem + "forward", *args, None)
+                op._call(prep, stem + "backward", *args, vp(up), op._ptr(grads))
+            elif "expect" in stem:
+                args = (*w, vp(bc), vp(lc))
+                op._call(prep, stem + "forward", *args, None, None, 1)
+                op._call(prep, stem + "backward", *args, vp(u0), vp(u1), op._ptr(grads))
+            else:
+                op._call(prep, stem + "forward", *w, None, 1)
+                op._call(prep, stem + "backward", w[0], vp(u0), op._ptr(grads))
+            got.append(grads.numpy().copy())
+        assert np.isfinite(got[0]).all() and np.count_nonzero(got[0]) > V, stem
+        assert got[0].tobytes() == got[1].tobytes(), (stem, shape)

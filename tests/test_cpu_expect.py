@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _expect_checks as C
+import _parity as P
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +62,9 @@ def test_padded_layout_bit_identical_to_packed(op, V):
 
 
 def test_absent_cost_arrays_and_no_grad(op):
-    """Either cost array may be None (zeros); both None: expected = 0. Without requires_grad the outputs are plain."""
+    """Either cost array may be None (zeros); both None: expected = 0. Without requires_grad the outputs are plain.
+    The gradient may be written over the logits (the C entry point, grads = acts)."""
+    P.check_gradient_in_place(op, "expect_")
     acts, labels, T, S, wb, we = C.small_problem(seed=70)
     zero = np.zeros_like(wb)
     for x, y, xz, yz in ((None, we, zero, we), (wb, None, wb, zero), (None, None, zero, zero)):

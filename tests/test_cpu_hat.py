@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import _hat_checks as H
+import _parity as P
 
 
 @pytest.fixture(scope="module")
@@ -76,7 +77,9 @@ def test_sample_path_costs(run, V, blank):
 
 
 def test_standard_loss_differs(run):
-    """The factorised distribution is another one: on the same logits the two losses disagree."""
+    """The factorised distribution is another one: on the same logits the two losses disagree. Its gradient, like
+    the standard one, may be written over the logits (the C entry point, grads = acts)."""
+    P.check_gradient_in_place(run.op, "hat_")
     acts, labels = H.problem(64, 0)
     c, _, _ = run.loss(acts, labels, 0, grads=False)
     lab, T, S = run.tensors(labels, False)

@@ -4,6 +4,7 @@ import pytest
 
 import _hat_checks as H
 import _hat_weight_checks as C
+import _parity as P
 
 DEV = C.Dev("cpu")
 VS = [5, 64, 512, 1024]
@@ -35,4 +36,7 @@ def test_restricting_alignment(V, blank):
 
 
 def test_reproducible_and_independent_of_the_batch():
+    """... and of where the gradient goes: it may be written over the logits (the C entry point, grads = acts)."""
+    import monotonic_rnnt_op
     C.check_expect_reproducible(DEV, 64, 47)
+    P.check_gradient_in_place(monotonic_rnnt_op, "hat_expect_")
