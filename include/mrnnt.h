@@ -434,7 +434,9 @@ const char *mrnnt_last_error(void);
 /* Number of in-band lattice rows whose acts the gradient kernel reads ("live" rows) for the problem of the
  * last mrnnt_forward(with_beta=1) on this workspace, written to *count_dev (device uint64). A row whose
  * occupancy exp(alpha(t-1,s) + beta(t,s) - ll) is below e^-110 has an exactly-zero fp32 gradient and is
- * stored without reading acts ("occ_skip" knob, on by default). Inspection/bench only; asynchronous. */
+ * stored without reading acts ("occ_skip" knob, on by default), and so is a row of mrnnt_backward whose every
+ * fp32 exponential flushes to zero (occupancy below about e^-87.35 and both arc corrections 0: the same bits
+ * either way). Inspection/bench only; asynchronous. */
 RNNTStatus mrnnt_grad_live_rows(const mrnnt_problem *p, const void *workspace, unsigned long long *count_dev,
                                 hipStream_t stream);
 

@@ -39,6 +39,14 @@ namespace {
 
 constexpr double kNegInf = -std::numeric_limits<double>::infinity();
 
+// the loss gradient's flush-dead rule (LossRows::row): always on in the product; the development build can switch it
+// off (mrnnt_cpu_flush_rows) to show that the gradient's bits do not depend on it
+#ifdef MRNNT_DEVTOOLS
+int g_flush_rows = 1;
+#else
+constexpr int g_flush_rows = 1;
+#endif
+
 // ---- SIMD row kernels ---------------------------------------------------------------------------------
 
 // e^x in fp32 from plain arithmetic (so the loops vectorise): Cody-Waite reduction by ln 2, degree-6
@@ -622,7 +630,8 @@ void grad_pass(const P &rows, float *grads, int nt) {
 //   g[v] = e^(z[v] + den + alpha(t-1,s) + beta(t,s) - ll) - [v == blank] e^(lpb + alpha(t-1,s) + beta(t+1,s) - ll)
 //          - [v == label(s), label != blank] e^(lpe + alpha(t-1,s) + beta(t+1,s+1) - ll),
 // times grad_scale[b]. Out-of-band rows are 0 * scale (NaN * scale for ll = -inf: the reference's exp(... - ll)),
-// in-band rows below the occupancy threshold (kDeadLogOcc) are exact zeros written without reading acts.
+// in-band rows below the occupancy threshold (kDeadLogOcc) are exact zeros written without reading acts, and so are
+// the rows whose every vexp flushes to 0 (kFlushLnCpu).
 struct LossRows : RowsBase {
     const float *scale;
     struct Col : ArcState {
@@ -640,15 +649,18 @@ struct LossRows : RowsBase {
         const double b0 = col.beta_at(s), base = col.alpha_in(s) - col.ll;
         fill = 0.0f * col.sc;
         if (base + b0 < mrnnt::kDeadLogOcc) return false;
-        const float c = (float)((double)w.den[r] + base + b0), sc = col.sc;
+        const float den = w.den[r];
+        const float c = (float)((double)den + base + b0), sc = col.sc;
+        const float cb = (float)std::exp(w.lpb[r] + base + col.beta_blank(s));
+        // (the label arc's state is read only where the formula below reads it: s < S, whatever the label is)
+        const float ce = s < col.S ? (float)std::exp(w.lpe[r] + base + col.beta_label(s)) : 0.0f;
+        // flush-dead (mrnnt_host.h kFlushLnCpu): every vexp below is exactly 0 and so are both corrections; the row
+        // is (0 - 0) * sc = fill, acts not read. A NaN anywhere compares false and takes the formula.
+        if (g_flush_rows && (double)c - (double)den < mrnnt::kFlushLnCpu && cb == 0.0f && ce == 0.0f) return false;
         const RowIO io = live();
         grad_row(io.z, io.g, pl.V, c, sc);
-        const float cb = (float)std::exp(w.lpb[r] + base + col.beta_blank(s));
         io.g[p->blank] = (vexp(io.zb + c) - cb) * sc;
-        if (io.l >= 0) {
-            const float ce = (float)std::exp(w.lpe[r] + base + col.beta_label(s));
-            io.g[io.l] = (vexp(io.zl + c) - ce) * sc;
-        }
+        if (io.l >= 0) io.g[io.l] = (vexp(io.zl + c) - ce) * sc;
         return true;
     }
 };
@@ -844,6 +856,15 @@ RNNTStatus mrnnt_cpu_hat_backward(const mrnnt_problem *p, const void *ws, const 
                                   int num_threads) {
     return cpu_backward_impl(p, ws, grad_scale, grads, num_threads, true);
 }
+
+#ifdef MRNNT_DEVTOOLS
+// development build only: the flush-dead rule of mrnnt_cpu_backward on (1) / off (0); < 0 asks; returns the previous
+__attribute__((visibility("default"))) int mrnnt_cpu_flush_rows(int on) {
+    const int prev = g_flush_rows;
+    if (on >= 0) g_flush_rows = on != 0;
+    return prev;
+}
+#endif
 
 RNNTStatus mrnnt_cpu_posteriors(const mrnnt_problem *p, const void *ws, float *blank_post, float *label_post, float *emit,
                                 int64_t emit_stride, float *label_time, int64_t time_stride, int num_threads) {

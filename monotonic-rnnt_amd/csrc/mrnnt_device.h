@@ -463,6 +463,13 @@ __device__ __forceinline__ float zero_row_value(double ll, float sc) {
 // The dead-row predicate (mrnnt_host.h kDeadLogOcc); NaN state is live.
 __device__ __forceinline__ bool row_live(double log_occ) { return !(log_occ < kDeadLogOcc); }
 
+// The flush-dead predicate of the stored-logits loss gradient (mrnnt_host.h kFlushLog2) on the coefficients a row
+// would be staged with and its stored denominator: every exp2 of the row returns +0. Any NaN makes the row live.
+__device__ __forceinline__ bool row_flush_dead(float c2, float den, float cb, float ce, int V) {
+    const double ub = fma(-(double)den, (double)kLog2e, (double)c2);  // (the product is exact in fp64)
+    return ub + flush_eps_log2((double)den, V) < kFlushLog2 && cb == 0.0f && ce == 0.0f;
+}
+
 __device__ __forceinline__ RowCoef row_coef(const DevProblem &p, int t, int T, int S, int s, int64_t row, double ll,
                                             const int *__restrict__ lab_b) {
     const int W = S + 1;

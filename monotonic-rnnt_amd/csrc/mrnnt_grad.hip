@@ -18,6 +18,12 @@ namespace mrnnt {
 // The loss's rows for the shared streamers (mrnnt_grad.h): band = the monotonic band of the column, a row's staged
 // coefficients {c2, cb, ce, label | kDeadRow} from row_coef, the other rows zero_row_value.
 struct LossRows {
+    // a row's acts are read: live under kDeadLogOcc and, with occ_skip = 1 (the product), not flush-dead either
+    // (mrnnt_host.h kFlushLog2; occ_skip = 2, development build: kDeadLogOcc alone)
+    static __device__ __forceinline__ bool alive(const DevProblem &p, const RowCoef &rc, int64_t row) {
+        return rc.live && !(p.occ_skip == 1 && row_flush_dead(rc.c2, p.den[row], rc.cb, rc.ce, p.V));
+    }
+
     struct Col {
         int T, lo, hi;
         double ll;
@@ -33,7 +39,7 @@ struct LossRows {
                                                const int *lab_b, Coef &rc) {
         const bool inb = s >= col.lo && s <= col.hi;
         if (inb) rc = row_coef(p, t, col.T, S, s, rowc + s, col.ll, lab_b);
-        return inb && rc.live;
+        return inb && alive(p, rc, rowc + s);
     }
 
     typedef float4 Slot;
@@ -42,7 +48,7 @@ struct LossRows {
         Slot cf = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(kDeadRow));
         if (s >= col.lo && s <= col.hi) {
             const RowCoef rc = row_coef(p, t, col.T, S, s, rowc + s, col.ll, lab_b);
-            if (rc.live) cf = make_float4(rc.c2, rc.cb, rc.ce, __int_as_float(rc.lab));
+            if (alive(p, rc, rowc + s)) cf = make_float4(rc.c2, rc.cb, rc.ce, __int_as_float(rc.lab));
         }
         return cf;
     }
@@ -125,7 +131,7 @@ __global__ __launch_bounds__(256) void grad_kernel(DevProblem p, const float *__
                 inb[r] = ok[r] && sr >= lo && sr <= hi;
                 if (inb[r]) {
                     rc[r] = row_coef(p, t, T, S, sr, rowc + sr, ll, lab_b);
-                    inb[r] = rc[r].live;  // dead rows are stored like out-of-band rows
+                    inb[r] = LossRows::alive(p, rc[r], rowc + sr);  // dead rows are stored like out-of-band rows
                 } else {
                     rc[r] = RowCoef{0.0f, 0.0f, 0.0f, -1, false};
                 }
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(256) void grad_rows_kernel(DevProblem p, const floa
         Vec *__restrict__ out = gv + row * (int64_t)VL;
         RowCoef rc;
         if (inb) rc = row_coef(p, t, T, S, s, row, p.ll[b], p.labels + (int64_t)b * p.label_stride);
-        if (!inb || !rc.live) {
+        if (!inb || !LossRows::alive(p, rc, row)) {
             const Vec zv = splat<IO>(zero_row_value(p.ll[b], sc));
             for (int j = lane; j < VL; j += 64) vstore<NTS>(out + j, zv);
             continue;
@@ -209,8 +215,9 @@ __global__ __launch_bounds__(256) void grad_rows_kernel(DevProblem p, const floa
     }
 }
 
-// Number of in-band rows whose acts the gradient kernels read (live rows; all in-band rows with
-// occ_skip = 0). Not on the hot path: bench/inspection only (mrnnt_grad_live_rows).
+// Number of in-band rows whose acts the gradient kernels read (LossRows::alive, the kernels' own predicate on the
+// coefficients they stage; all in-band rows with occ_skip = 0). Not on the hot path: bench/inspection only
+// (mrnnt_grad_live_rows).
 __global__ __launch_bounds__(256) void count_live_kernel(DevProblem p, unsigned long long *__restrict__ count) {
     resolve_dyn(p);
     __shared__ unsigned long long part[4];
@@ -226,9 +233,10 @@ __global__ __launch_bounds__(256) void count_live_kernel(DevProblem p, unsigned 
         const int lo = max(0, t - (T - S));
         const int hi = min(t, S);
         const double ll = p.ll[b];
+        const int *__restrict__ lab_b = p.labels + (int64_t)b * p.label_stride;
         for (int s = lo + threadIdx.x; s <= hi; s += blockDim.x) {
             const int64_t row = rowc + s;
-            n += (!p.occ_skip || row_live(alpha_prev(p, t, s, row, W) - ll + p.beta[row])) ? 1 : 0;
+            n += LossRows::alive(p, row_coef(p, t, T, S, s, row, ll, lab_b), row) ? 1 : 0;
         }
     }
 #pragma unroll

@@ -47,7 +47,7 @@ struct DevProblem {
     const int *min_s;           // [cols] alignment band (nullptr = unrestricted)
     const int *max_s;           // [cols]
     int B, V, blank;
-    int occ_skip;               // skip the acts read of rows whose gradient is exactly zero (mrnnt_grad.hip)
+    int occ_skip;               // skip the acts read of rows whose gradient is exactly zero (mrnnt_grad.hip): Tuning
     int64_t num_cols;           // sum_b T_b
     int64_t num_rows;           // N = sum_b T_b (S_b + 1)
     int64_t pad_T, pad_S1;      // padded acts layout (pad_S1 == 0: packed)
@@ -173,7 +173,8 @@ struct Tuning {
     int nt_store = 1;             // nontemporal stores of grads
     int nt_load = 2;              // loads of acts in both streaming kernels: 1 nontemporal, 0 default policy,
                                   // 2 by size (nt_acts_loads)
-    int occ_skip = 1;             // gradient: no acts read for rows with log-occupancy < kDeadLogOcc
+    int occ_skip = 1;             // gradient: no acts read for rows with log-occupancy < kDeadLogOcc, nor (the loss on
+                                  // stored logits) for flush-dead rows (kFlushLog2); 2 -> kDeadLogOcc alone, 0 -> no skip
     int joint_bwd_mfma = 16;      // fused joint backward MFMA tile for H <= 512: 16 (v_mfma_f32_16x16x32_bf16) or 32
                                   // (32x32x16, development build); H = 640 always 32
     int joint_reduce_sparse = 0;  // joint d_enc/d_pred reduce: 0 / 1 frame by frame, one workgroup per utterance and

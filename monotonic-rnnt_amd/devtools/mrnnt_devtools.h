@@ -27,6 +27,10 @@ int mrnnt_read_probe(const void *src, size_t bytes, void *sink, hipStream_t stre
  * the copy probe alone. */
 int mrnnt_write_probe(void *dst, size_t bytes, hipStream_t stream);
 
+/* y[i] = __builtin_amdgcn_exp2f(x[i]), the raw v_exp_f32 the gradient kernels' fast_exp2 issues: what the card
+ * returns where 2^x is below the smallest normal fp32 (the flush-dead row rule of mrnnt_host.h rests on it). */
+int mrnnt_exp2_probe(const float *x, float *y, int64_t n, hipStream_t stream);
+
 /* out[2 * slot] = the dispatch id the launch sees (the AQL packet index of its queue), out[2 * slot + 1] = its queue
  * address: what makes the chase launch's ready tags unique per launch, including HIP-graph replays. */
 int mrnnt_dispatch_probe(uint64_t *out, int slot, hipStream_t stream);

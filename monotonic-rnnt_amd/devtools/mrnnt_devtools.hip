@@ -107,6 +107,14 @@ __global__ __launch_bounds__(256) void occupy_kernel(uint64_t ticks) {
     while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
+// the raw v_exp_f32, exactly as the gradient kernels' fast_exp2 issues it (no denormal wrapper around it)
+__global__ __launch_bounds__(256) void exp2_probe_kernel(const float *__restrict__ x, float *__restrict__ y,
+                                                         int64_t n) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        y[i] = __builtin_amdgcn_exp2f(x[i]);
+}
+
 // slab size and grid of the probes: 32 workgroups per CU, each streaming >= 8 slabs in turn (a single pass
 // of one slab per workgroup measures the launch tail, not the memory); slabs of 16 KiB .. 800 KiB
 int probe_grid(int64_t n, int64_t *slab, int64_t *blocks) {
@@ -175,6 +183,15 @@ int mrnnt_write_probe(void *dst, size_t bytes, hipStream_t stream) {
     const hipError_t stale = hipGetLastError();
     write_probe_kernel<<<(int)blocks, 256, 0, stream>>>(static_cast<u4 *>(dst), n, slab);
     return launch_status("write probe", stale);
+}
+
+int mrnnt_exp2_probe(const float *x, float *y, int64_t n, hipStream_t stream) {
+    if (n <= 0) return 0;
+    if (!x || !y) return 2;
+    const int64_t blocks = std::min<int64_t>((n + 255) / 256, 65536);
+    const hipError_t stale = hipGetLastError();
+    exp2_probe_kernel<<<(int)blocks, 256, 0, stream>>>(x, y, n);
+    return launch_status("exp2 probe", stale);
 }
 
 int mrnnt_dispatch_probe(uint64_t *out, int slot, hipStream_t stream) {

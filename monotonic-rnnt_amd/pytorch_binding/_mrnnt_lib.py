@@ -298,6 +298,8 @@ def devtools() -> ctypes.CDLL:
             t.mrnnt_write_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
             t.mrnnt_read_probe.restype = ctypes.c_int
             t.mrnnt_read_probe.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+            t.mrnnt_exp2_probe.restype = ctypes.c_int
+            t.mrnnt_exp2_probe.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
             t.mrnnt_dispatch_probe.restype = ctypes.c_int
             t.mrnnt_dispatch_probe.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
             t.mrnnt_occupy.restype = ctypes.c_int

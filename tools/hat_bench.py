@@ -13,7 +13,9 @@ together with the two library steps (the ratio of record). A last pass with the 
 launches' own times. Two counts say how many rows either gradient pass had to read and write -- the two distributions
 spread their paths over different numbers of rows (on N(0,1) logits a factorised blank has probability 1/2, a softmax
 blank 1/V): the rows of the gradient that are not all zero, and mrnnt_grad_live_rows on the state of either forward
-(occupancy >= e^-110, the standard loss's rule). Prints one JSON object.
+(the standard loss's rule, LossRows::alive: occupancy >= e^-110 and not flush-dead, i.e. not every fp32 exponential of
+the row zero -- mrnnt_host.h kFlushLog2; it is evaluated on whatever den the forward left, so after the factorised
+forward the count is that predicate on den', not HatRows' own). Prints one JSON object.
 """
 import argparse
 import ctypes
