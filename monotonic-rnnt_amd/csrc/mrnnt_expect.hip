@@ -298,7 +298,7 @@ struct RowLoaded {
 // utterance whose ll is not finite holds NaN. Rows outside the band are not written.
 // The loads of a row do not depend on one another and none sits behind a branch: a lane past the band's end, the
 // first / last frame and s = S load a clamped address (the row itself, or the band's last row) and the boundary value
-// is selected afterwards, so the ten loads are issued together and waited for once (build_row's rule, mrnnt_joint.hip).
+// is selected afterwards, so the ten loads are issued together and waited for once (build_row's rule, mrnnt_joint_tile.h).
 // Everything they touch is allocated and initialised: alpha / beta / A / Bk over the band, lp zero-filled by the joint
 // forward, the cost arrays over the caller's grid (the label cost of s = S_b is addressed at s = S_b - 1; a value the
 // contract calls never-read -- S_b = 0, a dead row -- may be loaded and is then dropped by a select, never multiplied).

@@ -88,7 +88,7 @@ struct DevProblem {
 // rows of the caller's grads buffer a gradient launch covers (host bound)
 inline int64_t grads_rows(const DevProblem &p) { return p.pad_S1 ? (int64_t)p.B * p.pad_T * p.pad_S1 : p.num_rows; }
 
-// Fused joint network (mrnnt_joint.hip): logits z(b,t,s,:) = W * tanh(enc[b,t,:] + pred[b,s,:]) + bias are
+// Fused joint network (mrnnt_joint*.hip): logits z(b,t,s,:) = W * tanh(enc[b,t,:] + pred[b,s,:]) + bias are
 // formed on MFMA inside the log-softmax and gradient passes and never stored. Operands are bf16 bit patterns.
 struct JointArgs {
     const unsigned short *enc;   // [B, *, H]: row (b, t) at enc + b*enc_sb + t*H
@@ -157,6 +157,14 @@ hipError_t launch_joint_tail_zero(unsigned short *G, int V, unsigned short *Hact
 size_t joint_min_lds_bytes(int H, int V);
 // ... and the 16x16x32 backward when it sums dbias (one column-sum row per wave more)
 size_t joint_dbias_lds_bytes(int H, int V);
+// Before a launch with `bytes` of dynamic LDS: past the 64 KiB every kernel may have, the kernel has to be allowed it
+// (no launch with too little LDS: the attribute's failure is the call's error)
+template <class Kernel>
+inline hipError_t allow_lds(Kernel kern, size_t bytes) {
+    if (bytes <= 65536) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes);
+}
 
 // Launch-shape knobs (experiment hook: mrnnt_tune in mrnnt_capi.cpp). Defaults are the tuned values.
 struct Tuning {
@@ -203,7 +211,7 @@ struct Tuning {
     int chase_early_free = 1;     // staged chase walk: ring slots freed when read into registers (0: after their use)
     int chase_ring = 64;          // staged chase walk: cap on the LDS ring's frames (16: round 5's depth)
     int joint_reduce_hact = 1;    // joint reduce: 1 reads Hact; 0 (development build) recomputes the activation from
-                                  // enc / pred (the gradient pass's bits; measured slower, mrnnt_joint.hip)
+                                  // enc / pred (the gradient pass's bits; measured slower, mrnnt_joint_reduce.hip)
     int joint_reduce_pad = 1;     // joint reduce: accumulator LDS pitch HS + 1 (0: HS, development A/B; bit-identical)
     int joint_trace = 0;          // development build: the joint forward with its timeline stamps (tools/joint_trace.py)
     int joint_probe = 0;          // development probe: JointArgs::probe of the joint forward (results wrong)

@@ -1,6 +1,6 @@
 // mrnnt_joint_capi.cpp -- the fused joint network + loss ABI of libmonotonic_rnnt_amd.so (mrnnt_joint_* in
-// include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint.hip,
-// mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors / mrnnt_joint_sample put the Viterbi launch / the
+// include/mrnnt.h): the loss plan of mrnnt_plan.h extended by the row lists of the joint kernels (mrnnt_joint_rows.hip;
+// mrnnt_joint.hip, mrnnt_joint_reduce.hip, mrnnt_joint_gemm.hip). mrnnt_joint_align / mrnnt_joint_posteriors / mrnnt_joint_sample put the Viterbi launch / the
 // posterior read-out / the path sampler of the loss ABI behind the joint's log-softmax pass; mrnnt_joint_path_* score
 // given alignments (mrnnt_path.hip's walk / hull / score / coef launches around the joint pass over the hull rows) and
 // run the gradient pass over the path-live rows; mrnnt_joint_expect_* put the expectation recursion of

@@ -492,8 +492,7 @@ static hipError_t launch_dpre_k16(const unsigned short *G, const unsigned short 
     const int64_t blocks = ((rtiles + 7) / 8) * 8 * (H / kGT);
     if (blocks > 0x7fffffff / 512) return hipErrorInvalidValue;
     auto kern = joint_dpre_k16_kernel<NS, PRIO, IL, HP>;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = allow_lds(kern, lds);
     if (e != hipSuccess) return e;
     kern<<<(unsigned)blocks, 512, lds, stream>>>(G, Wt, Hact, hact_ld, dpre, n, V, H);
     return hipGetLastError();
@@ -666,8 +665,7 @@ static hipError_t launch_dpre_nw(const unsigned short *G, const unsigned short *
     const int64_t blocks = ((rtiles + 7) / 8) * 8 * (H / kGT);  // (row tile, h-half) pairs in XCD order; extras exit
     if (blocks > 0x7fffffff / 512) return hipErrorInvalidValue;
     auto kern = joint_dpre_kernel<NW, RT, NS, WPE, EPI>;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = allow_lds(kern, lds);
     if (e != hipSuccess) return e;
     kern<<<(unsigned)blocks, 64 * NW, lds, stream>>>(G, Wt, Hact, hact_ld, dpre, n, V, H, tuning().joint_dpre_abl);
     return hipGetLastError();
@@ -817,8 +815,7 @@ static hipError_t launch_dpre_persist(const unsigned short *G, const unsigned sh
                                       int64_t hact_ld, unsigned short *dpre, int64_t n, int V, int H, int64_t slots,
                                       hipStream_t stream) {
     const size_t lds = (size_t)kDStages * kDImage;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(joint_dpre_persist_kernel<TAILV>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = allow_lds(joint_dpre_persist_kernel<TAILV>, lds);
     if (e != hipSuccess) return e;
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
@@ -834,8 +831,7 @@ static hipError_t launch_dpre_direct(const unsigned short *G, const unsigned sho
                                      int64_t hact_ld, unsigned short *dpre, int64_t n, int V, int H, int64_t blocks,
                                      hipStream_t stream) {
     const size_t lds = (size_t)kDStages * kDImage;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(joint_dpre_direct_kernel<TAILV>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = allow_lds(joint_dpre_direct_kernel<TAILV>, lds);
     if (e != hipSuccess) return e;
     joint_dpre_direct_kernel<TAILV><<<(unsigned)blocks, 512, lds, stream>>>(G, Wt, Hact, hact_ld, dpre, n, V, H);
     return hipGetLastError();

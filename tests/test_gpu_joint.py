@@ -11,6 +11,7 @@ Tolerances (floating-point extension on bf16 matrix cores, stated here):
   grads : max |dg| <= 1.5e-2 * max |g_ref| + 1e-5 per tensor (the logit gradient is stored as bf16, 2^-9 relative,
                                          and dH = G weight runs as a bf16 GEMM)
 """
+import contextlib
 import os
 
 import numpy as np
@@ -451,14 +452,20 @@ def test_joint_masked_bias(jop, dev):
         assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("H,V", [(512, 1024), (256, 1000), (640, 130)])
-def test_joint_plain_exp_sum_matches_running_max(dev, H, V):
+@pytest.mark.parametrize("H,V,route", [(512, 1024, "scaled"), (256, 1000, "scaled"), (640, 130, "scaled"),
+                                       (256, 1000, "unscaled"), (640, 130, "unscaled")],
+                         ids=["512-1024", "256-1000", "640-130", "256-1000-unscaled", "640-130-unscaled"])
+def test_joint_plain_exp_sum_matches_running_max(dev, H, V, route):
     """Bounded weights: the plain exp-sum forward (product) against the running-max epilogue forced on (development
     build, joint_probe bit 3) on the same inputs: costs within 1e-6 relative (the two fp32 sums differ only in
-    rounding), gradients within 2^-7 of their max (bf16 logit-gradient rounding can flip)."""
+    rounding), gradients within 2^-7 of their max (bf16 logit-gradient rounding can flip). Route "unscaled": the plain
+    exp-sum without the prescaled bias row (development build, joint_opt = 1), which the product takes only where two
+    weight tiles and two bias rows pass 160 KiB (H = 640, V > 10240), at the shapes with a ragged tail chunk on either
+    backward tile."""
     import monotonic_rnnt_joint as jm
     enc, pred, w, bias, labels, T, S = make_case(H * 3 + V, 3, (20, 60), 20, H, V)
-    a = run_joint(jm, dev, enc, pred, w, bias, labels, T, S, scale=[1.0, -0.5, 2.0])
+    with knobs(joint_opt=1) if route == "unscaled" else contextlib.nullcontext():
+        a = run_joint(jm, dev, enc, pred, w, bias, labels, T, S, scale=[1.0, -0.5, 2.0])
     with knobs(joint_probe=8):
         b = run_joint(jm, dev, enc, pred, w, bias, labels, T, S, scale=[1.0, -0.5, 2.0])
     assert np.all(np.abs(a[0] - b[0]) <= 1e-6 * np.maximum(1.0, np.abs(b[0]))), (a[0], b[0])

@@ -1,5 +1,6 @@
 """monotonic_rnnt_joint_expected_cost (mrnnt_joint_expect_*: the joint pass, the expectation recursion, the coefficient
-launch of mrnnt_expect.hip, the expect-live row list and the MFMA gradient pass of mrnnt_joint.hip) against the
+launch of mrnnt_expect.hip, the expect-live row list of mrnnt_joint_rows.hip and the MFMA gradient pass of
+mrnnt_joint.hip) against the
 yardstick of tests/_joint_expect_checks.py -- the fp64 composition the fused op replaces, from the same bf16 inputs --
 and against the library's own read-outs and unfused twin.
 

@@ -1,17 +1,25 @@
 #!/usr/bin/env python3
-"""Per-kernel register / spill / occupancy table of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
+"""Per-kernel register / spill / occupancy table of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage),
+compiled with the flags monotonic-rnnt_amd/Makefile gives that file's object (JOINT_FLAGS for the mrnnt_joint* units
+included): the table of the kernels the library ships.
 
-usage: python tools/resource_usage.py monotonic-rnnt_amd/csrc/mrnnt_grad.hip [filter]
+usage: python tools/resource_usage.py [--dev] monotonic-rnnt_amd/csrc/mrnnt_grad.hip [filter]
+  --dev   the development flavour (-DMRNNT_DEVTOOLS: libmonotonic_rnnt_amd_dev.so)
 """
 import re, subprocess, sys, os
 
 here = os.path.dirname(os.path.abspath(__file__))
-pkg = os.path.join(here, "..", "monotonic-rnnt_amd")
-src = sys.argv[1]
-flt = sys.argv[2] if len(sys.argv) > 2 else ""
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950",
-       "-I" + os.path.join(pkg, "..", "include"), "-I" + os.path.join(pkg, "csrc"),
-       "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+pkg = os.path.abspath(os.path.join(here, "..", "monotonic-rnnt_amd"))
+args = [a for a in sys.argv[1:] if a != "--dev"]
+dev = "--dev" in sys.argv[1:]
+src = args[0]
+flt = args[1] if len(args) > 1 else ""
+# the compile line `make` would run for this file's object, with the object and its output left out
+obj = os.path.join(pkg, "build", "dev" if dev else "", os.path.splitext(os.path.basename(src))[0] + ".o")
+plan = subprocess.run(["make", "-n", "-B", "-C", pkg, obj], capture_output=True, text=True, check=True).stdout
+line = next(l for l in plan.splitlines() if " -c " in l and l.rstrip().endswith("-o " + obj))
+cmd = line.split()
+cmd = cmd[:cmd.index("-c")] + ["-c", os.path.abspath(src), "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
